@@ -1,8 +1,9 @@
 """Flagship benchmark: MNIST-CNN Stage samples/sec on MI355X.
 
 Measures the BASELINE.json headline metric — samples/sec (whole node) of
-the MNIST-CNN training Stage — plus the secondary configs (ResNet-50
-bf16, GPT-2 small). Synthetic data (no network access), random-init
+the MNIST-CNN training Stage. The secondary configs (ResNet-50 bf16,
+GPT-2 small) are separate invocations selected with --model; one run
+measures one config. Synthetic data (no network access), random-init
 weights.
 
 Launch (driver contract):
@@ -21,6 +22,14 @@ gradient sync a single RCCL all-reduce, and the whole step is captured
 into a hipGraph and replayed — per-step host work is one small D2D batch
 copy plus one graph launch. --impl ddp runs the torch-DDP eager path for
 comparison.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the result line. --dump-outputs DIR additionally
+writes what the last timed step computed (loss.npy, params.npy,
+grads.npy; float32) so two builds can be compared output for output —
+model init and the synthetic batches are seeded, so the inputs are
+identical from run to run. --full is reserved for measurements beyond the
+headline figure.
 """
 
 import argparse
@@ -74,7 +83,49 @@ def parse_args():
         help='track N distributed reduced metrics per step (BASELINE config #5: '
         'ResNet-50 bs=8192 reducer stress — combine with --model resnet50 --batch-size 8192)',
     )
+    p.add_argument(
+        '--dump-outputs',
+        default=None,
+        metavar='DIR',
+        help='after the timed steps, write what the last timed step computed (loss, updated '
+        'parameters, gradients) to DIR/<name>.npy as float32',
+    )
+    p.add_argument(
+        '--full',
+        action='store_true',
+        help='also run the measurements beyond the headline figure; a plain run only sets up, '
+        'warms up, times the steps and prints the result line (there are none at present: '
+        'secondary configs are separate runs selected with --model/--impl)',
+    )
     return p.parse_args()
+
+
+# --dump-outputs budget: 64 MB in all -> two sampled fp32 arrays of <= 24 MB each
+DUMP_MAX_ELEMS = 6_000_000
+
+
+def dump_outputs(out_dir, stage):
+    """Write the results of the last timed step as float32 .npy files:
+    its loss, and the parameters and gradients it left behind (in
+    registration order, flattened and concatenated). Arrays above
+    DUMP_MAX_ELEMS are reduced to a fixed seeded sample of their elements,
+    so two runs with the same arguments dump the same positions."""
+    import numpy as np
+
+    def flat32(tensors):
+        return torch.cat([t.detach().reshape(-1).to(torch.float32) for t in tensors]).cpu().numpy()
+
+    def sample(a):
+        if a.size <= DUMP_MAX_ELEMS:
+            return a
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+        return a[idx]
+
+    params = list(stage.pipeline.models['net'].parameters())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), flat32([stage.last_loss]))
+    np.save(os.path.join(out_dir, 'params.npy'), sample(flat32(params)))
+    np.save(os.path.join(out_dir, 'grads.npy'), sample(flat32([p.grad for p in params if p.grad is not None])))
 
 
 class BenchStage(TrainValStage):
@@ -221,6 +272,9 @@ class BenchStage(TrainValStage):
         else:
             loss = self.train_step((self.static_batch, self.static_labels))
         self.optimize(loss)
+        # kept for --dump-outputs; under graph replay this static tensor
+        # holds the loss of the latest replayed step
+        self.last_loss = loss.detach()
         self.track_reduce(self.loss_metric_name(), loss)
         if self.args.metric_stress:
             # BASELINE config #5: N device-resident reducer accumulations
@@ -344,6 +398,9 @@ def main():
         metric, value = 'tokens/s', samples_per_sec * args.seq_len
     else:
         metric, value = 'samples/s', samples_per_sec
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, stage)
 
     if rank == 0:
         result = {

@@ -12,7 +12,7 @@
 //   v2  LDS-staged per-sample workgroups           -> bwd_weight-dominated.
 //   v3  halo-padded planes (branch-free taps), bank-skewed strides,
 //       chunked bwd_weight: fwd 1439us / bwd_data 1199us / bwd_w 914us.
-//   v4  (this file) instruction-count pass:
+//   v4  instruction-count pass:
 //       - fwd computes a 2x2 POOLED block per thread from a 6x6 window
 //         read as ds_read_b128+b64 rows (12 LDS instructions per channel
 //         instead of 64 b32), 4x fewer address computations;
@@ -23,6 +23,11 @@
 //         stage time, inner loop reads 2 LDS values per cell + 9 taps.
 //       Padded geometry guarantees every vector read is 16B-aligned
 //       (guide §17) and channel strides are bank-skewed (mod 64 != 0).
+//   v4+ (this file) bwd_weight ends in one row of partials per workgroup
+//       and an ordered second-stage sum instead of one atomicAdd per tap
+//       per workgroup: run-to-run reproducible gradients; full model step
+//       at batch 16384 1.84 ms -> 1.53-1.61 ms
+//       (profiles/smallcnn_bwdw_ordered_partials.md).
 //
 // ReLU/maxpool tie-breaking matches torch: first index wins ties, and a
 // pooled value of exactly 0 (all-negative window) propagates no gradient.
@@ -279,12 +284,15 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_data_kernel(
 // Workgroup = chunk of `samples` samples looped through LDS. The pool
 // gradient is pre-gated at stage time into dense per-cell (g, sub) pairs
 // (g = 0 encodes "no gradient"). Thread owns ((co,ci), slice): 9 register
-// partials across the chunk; LDS tree across slices; one atomicAdd per
-// tap per workgroup.
+// partials across the chunk(s); LDS tree across slices; the workgroup
+// then writes ONE row of partials {dw[pairs*9], db[COUT]} to `part`
+// (row = blockIdx.x). bwd_weight_reduce_kernel sums the rows in a fixed
+// order: no atomics, so the gradient does not depend on the order in which
+// workgroups finish and is bitwise reproducible from run to run.
 __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
     const float* __restrict__ dpooled, const uint8_t* __restrict__ argmax,
-    const float* __restrict__ pooled, const float* __restrict__ in, float* __restrict__ dw,
-    float* __restrict__ db, int N, int CIN, int COUT, int H, int W, int samples) {
+    const float* __restrict__ pooled, const float* __restrict__ in, float* __restrict__ part,
+    int N, int CIN, int COUT, int H, int W, int samples) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const PlaneGeom pg = plane_geom(H, W);
   const int iplane = CIN * H * W;
@@ -306,9 +314,6 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
   const int ci = pair % CIN;
   const bool active = threadIdx.x < pairs * nslices;
 
-  const int n0 = blockIdx.x * samples;
-  const int nvalid = min(samples, N - n0);
-
   float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   float accb = 0.0f;
 
@@ -316,49 +321,56 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
   for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f;
   __syncthreads();
 
-  for (int s = 0; s < nvalid; ++s) {
-    const int64_t n = n0 + s;
-    fill_plane_padded(in + n * iplane, ilds, CIN, H, W, pg);
-    for (int cell = threadIdx.x; cell < cells; cell += kBlock) {
-      const int64_t pidx = n * cells + cell;
-      const int cco = cell / pcells;
-      const int rem = cell - cco * pcells;
-      const float pv = pooled[pidx];
-      glds[cco * pstride + rem] = (pv > 0.0f) ? dpooled[pidx] : 0.0f;
-      // pre-decode the argmax into a padded-plane offset so the hot loop
-      // below needs no div/mod per cell (offsets < 2048 are exact floats)
-      const int sub = argmax[pidx];
-      const int px = rem % PW;
-      const int py = rem / PW;
-      const int yy = 2 * py + (sub >> 1);
-      const int xx = 2 * px + (sub & 1);
-      slds[cco * pstride + rem] = (float)(yy * pg.PADW + xx);
-    }
-    __syncthreads();
+  // chunk blockIdx.x and, when the grid was capped, every gridDim.x-th
+  // chunk after it; all chunks of a workgroup share its accumulators
+  const int nchunks = (N + samples - 1) / samples;
+  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int n0 = chunk * samples;
+    const int nvalid = min(samples, N - n0);
+    for (int s = 0; s < nvalid; ++s) {
+      const int64_t n = n0 + s;
+      fill_plane_padded(in + n * iplane, ilds, CIN, H, W, pg);
+      for (int cell = threadIdx.x; cell < cells; cell += kBlock) {
+        const int64_t pidx = n * cells + cell;
+        const int cco = cell / pcells;
+        const int rem = cell - cco * pcells;
+        const float pv = pooled[pidx];
+        glds[cco * pstride + rem] = (pv > 0.0f) ? dpooled[pidx] : 0.0f;
+        // pre-decode the argmax into a padded-plane offset so the hot loop
+        // below needs no div/mod per cell (offsets < 2048 are exact floats)
+        const int sub = argmax[pidx];
+        const int px = rem % PW;
+        const int py = rem / PW;
+        const int yy = 2 * py + (sub >> 1);
+        const int xx = 2 * px + (sub & 1);
+        slds[cco * pstride + rem] = (float)(yy * pg.PADW + xx);
+      }
+      __syncthreads();
 
-    if (active) {
-      const float* ip = ilds + ci * pg.cs;
-      const float* gp = glds + co * pstride;
-      const float* sp = slds + co * pstride;
-      for (int cell = slice; cell < pcells; cell += nslices) {
-        // branchless: g == 0 cells contribute 0 to every accumulator, and
-        // their stored offset still addresses in-bounds LDS — skipping
-        // them would diverge the wave at 16-lane granularity
-        const float g = gp[cell];
-        const int off = (int)sp[cell];
-        if (ci == 0) accb += g;
-        // input rows yy-1..yy+1 -> padded rows yy..yy+2, cols likewise
-        const float* iw = ip + off;
+      if (active) {
+        const float* ip = ilds + ci * pg.cs;
+        const float* gp = glds + co * pstride;
+        const float* sp = slds + co * pstride;
+        for (int cell = slice; cell < pcells; cell += nslices) {
+          // branchless: g == 0 cells contribute 0 to every accumulator, and
+          // their stored offset still addresses in-bounds LDS — skipping
+          // them would diverge the wave at 16-lane granularity
+          const float g = gp[cell];
+          const int off = (int)sp[cell];
+          if (ci == 0) accb += g;
+          // input rows yy-1..yy+1 -> padded rows yy..yy+2, cols likewise
+          const float* iw = ip + off;
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
+          for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
-          for (int kx = 0; kx < 3; ++kx) {
-            acc[ky * 3 + kx] = fmaf(g, iw[ky * pg.PADW + kx], acc[ky * 3 + kx]);
+            for (int kx = 0; kx < 3; ++kx) {
+              acc[ky * 3 + kx] = fmaf(g, iw[ky * pg.PADW + kx], acc[ky * 3 + kx]);
+            }
           }
         }
       }
+      __syncthreads();
     }
-    __syncthreads();
   }
 
   // cross-slice reduction (skipped when nslices == 1)
@@ -384,9 +396,41 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
   }
 
   if (active && slice == 0) {
+    float* row = part + (int64_t)blockIdx.x * (pairs * 9 + COUT);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) atomicAdd(&dw[pair * 9 + k], acc[k]);
-    if (ci == 0 && db != nullptr) atomicAdd(&db[co], accb);
+    for (int k = 0; k < 9; ++k) row[pair * 9 + k] = acc[k];
+    if (ci == 0) row[pairs * 9 + co] = accb;
+  }
+}
+
+// Sums the `rows` partial rows of `part` [rows][cols] column by column in a
+// fixed order and ADDS the totals to dw (cols < ndw) / db (the rest; may be
+// null). Workgroup = kRedCols columns x kRedGroups row groups: a thread
+// sums rows g, g + kRedGroups, ... of its column, then group 0 combines
+// the kRedGroups partials through LDS in ascending order.
+constexpr int kRedCols = 16;
+constexpr int kRedGroups = kBlock / kRedCols;
+__global__ void __launch_bounds__(kBlock) bwd_weight_reduce_kernel(
+    const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ db, int rows,
+    int cols, int ndw) {
+  __shared__ float red[kRedGroups][kRedCols + 1];
+  const int c = threadIdx.x % kRedCols;
+  const int g = threadIdx.x / kRedCols;
+  const int col = blockIdx.x * kRedCols + c;
+  float total = 0.0f;
+  if (col < cols) {
+#pragma unroll 8
+    for (int r = g; r < rows; r += kRedGroups) total += part[(int64_t)r * cols + col];
+  }
+  red[g][c] = total;
+  __syncthreads();
+  if (g == 0 && col < cols) {
+    for (int j = 1; j < kRedGroups; ++j) total += red[j][c];
+    if (col < ndw) {
+      dw[col] += total;
+    } else if (db != nullptr) {
+      db[col - ndw] += total;
+    }
   }
 }
 
@@ -449,7 +493,11 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
   const int lds_bytes =
       (CIN * pg.cs + 2 * COUT * pstride + kBlock) * (int)sizeof(float);
   TORCH_CHECK(lds_bytes <= kMaxLds, "bwd_weight staging exceeds LDS (", lds_bytes, " B)");
-  // chunk so that the grid stays ~>= 512 blocks while cutting atomics
+  TORCH_CHECK(dw.is_contiguous() && dw.scalar_type() == at::kFloat &&
+                  dw.numel() == (int64_t)COUT * CIN * 9,
+              "dw must be contiguous fp32 [COUT,CIN,3,3]");
+  TORCH_CHECK(!db.defined() || (db.is_contiguous() && db.numel() == COUT), "db must be [COUT]");
+  // chunk so that the grid stays ~>= 512 blocks while cutting partial rows
   // (DMLCLOUD_SMALLCNN_BWDW_CHUNK overrides for tuning experiments)
   int samples = 1;
   if (const char* env = std::getenv("DMLCLOUD_SMALLCNN_BWDW_CHUNK")) {
@@ -457,12 +505,20 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
   } else {
     while (samples < 16 && (N + samples * 2 - 1) / (samples * 2) >= 512) samples *= 2;
   }
-  const int blocks = (N + samples - 1) / samples;
+  if (N == 0) return;
+  // one partial row per workgroup; the grid cap bounds the workspace
+  const int blocks = std::min((N + samples - 1) / samples, kMaxGrid);
+  const int ndw = COUT * CIN * 9;
+  const int cols = ndw + COUT;
+  at::Tensor part = at::empty({blocks, cols}, dw.options());
   auto stream = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(conv3x3_relu_pool_bwd_weight_kernel, dim3(blocks), dim3(kBlock), lds_bytes,
                      stream, dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(),
-                     pooled.data_ptr<float>(), in.data_ptr<float>(), dw.data_ptr<float>(),
-                     db.defined() ? db.data_ptr<float>() : nullptr, N, CIN, COUT, H, W, samples);
+                     pooled.data_ptr<float>(), in.data_ptr<float>(), part.data_ptr<float>(), N,
+                     CIN, COUT, H, W, samples);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((cols + kRedCols - 1) / kRedCols),
+                     dim3(kBlock), 0, stream, part.data_ptr<float>(), dw.data_ptr<float>(),
+                     db.defined() ? db.data_ptr<float>() : nullptr, blocks, cols, ndw);
 }
 
 } // namespace dmlamd

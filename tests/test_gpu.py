@@ -361,6 +361,46 @@ class TestFusedCnn:
         torch.testing.assert_close(layer.bias.grad, b2.grad, rtol=1e-4, atol=1e-4)
         torch.testing.assert_close(x.grad, x2.grad, rtol=1e-4, atol=1e-4)
 
+    @pytest.mark.parametrize(
+        'cin,cout,hw,n,chunk',
+        [
+            (3, 4, 8, 2051, '1'),  # 2051 one-sample chunks > the 2048-workgroup grid cap
+            (2, 3, 8, 1031, None),  # default chunking: 2 samples/chunk, last chunk partial
+        ],
+    )
+    def test_weight_grad_many_workgroups_reproducible(self, cin, cout, hw, n, chunk, monkeypatch):
+        """The weight/bias gradient is summed over many workgroups through
+        ordered partial rows: it matches an fp64 torch oracle and is
+        bitwise identical from call to call."""
+        import torch.nn.functional as F
+
+        from dmlcloud_amd.ops.fused_cnn import ConvReluPool2d
+
+        if chunk is not None:
+            monkeypatch.setenv('DMLCLOUD_SMALLCNN_BWDW_CHUNK', chunk)
+        torch.manual_seed(2)
+        layer = ConvReluPool2d(cin, cout, first_layer=True).to(DEV)
+        x = torch.randn(n, cin, hw, hw, device=DEV)
+        g = torch.randn(n, cout, hw // 2, hw // 2, device=DEV)
+
+        grads = []
+        for _ in range(2):
+            layer.zero_grad(set_to_none=True)
+            layer(x).backward(g)
+            grads.append((layer.weight.grad.clone(), layer.bias.grad.clone()))
+        assert torch.equal(grads[0][0], grads[1][0])
+        assert torch.equal(grads[0][1], grads[1][1])
+
+        w2 = layer.weight.detach().double().requires_grad_(True)
+        b2 = layer.bias.detach().double().requires_grad_(True)
+        F.max_pool2d(F.relu(F.conv2d(x.double(), w2, b2, padding=1)), 2).backward(g.double())
+        # test_backward_matches_torch allows atol 1e-4 at n=4; the rounding
+        # error of a random-sign fp32 sum grows with the square root of the
+        # number of terms, i.e. with sqrt(n / 4)
+        atol = 1e-4 * (n / 4) ** 0.5
+        torch.testing.assert_close(grads[0][0].double(), w2.grad, rtol=1e-4, atol=atol)
+        torch.testing.assert_close(grads[0][1].double(), b2.grad, rtol=1e-4, atol=atol)
+
     def test_full_model_matches_eager(self):
         """FusedMnistCNN step == plain-torch mnist_cnn step (same weights)."""
         from dmlcloud_amd.models import mnist_cnn

@@ -310,7 +310,7 @@ def _pipeline_two_ranks(rank, world_size, tmpdir):
             self.loss = torch.nn.CrossEntropyLoss()
 
         def step(self, batch):
-            x, y = batch
+            x, y = (t.to(self.device) for t in batch)
             return self.loss(self.pipeline.models['m'](x), y)
 
     pipeline = TrainingPipeline()

@@ -28,7 +28,7 @@ class Stage_(TrainValStage):
         self.loss = torch.nn.CrossEntropyLoss()
 
     def step(self, batch):
-        x, y = batch
+        x, y = (t.to(self.device) for t in batch)
         return self.loss(self.pipeline.models['m'](x), y)
 
 
@@ -60,7 +60,7 @@ class TestCheckpointIntegration:
         # fresh pipeline resumes from the saved state
         pipeline2 = TrainingPipeline(name='ckpt2')
         pipeline2.checkpoint_dir = pipeline.checkpoint_dir
-        pipeline2.device = torch.device('cpu')
+        pipeline2.device = pipeline.device
         stage2 = Stage_()
         pipeline2.append_stage(stage2, max_epochs=2)
         stage2.pre_stage()
@@ -136,7 +136,7 @@ class TestFlatCheckpointRoundtrip:
                 self.loss = torch.nn.CrossEntropyLoss()
 
             def step(self, batch):
-                x, y = batch
+                x, y = (t.to(self.device) for t in batch)
                 return self.loss(self.pipeline.models['m'](x.to(torch.bfloat16)).float(), y)
 
         pipeline = TrainingPipeline(config={'seed': 0}, name='flatckpt')
@@ -205,7 +205,7 @@ class TestFlatBf16Cpu:
                 self.loss = torch.nn.CrossEntropyLoss()
 
             def step(self, batch):
-                x, y = batch
+                x, y = (t.to(self.device) for t in batch)
                 out = self.pipeline.models['m'](x.to(torch.bfloat16))
                 return self.loss(out.float(), y)
 
