@@ -104,6 +104,168 @@ def flash_attn_bwd_tiled(
     return dq, dk, dv
 
 
+# ---------------------------------------------------------------------------
+# Ragged-N emulation of the kernels' <kRagged = true> instantiations
+# ---------------------------------------------------------------------------
+#
+# The HIP kernels never shorten a tile. When N is not a multiple of 64 a
+# tile that hangs over the end of the sequence is still walked in full:
+# its row loads are CLAMPED to N - 1 (so they re-read the last real row),
+# the duplicated rows are MASKED out of the math, and stores are
+# PREDICATED on row < N. The two functions below do exactly that, with
+# the kernels' block / wave / sub-tile row ranges and loop bounds, so the
+# masking logic can be proved on the CPU. Names follow attention.hip.
+
+_NEG = -1e30  # the kernels' finite "minus infinity"
+_LOG2E = 1.44269504
+
+
+def _crow(rows: torch.Tensor, n: int) -> torch.Tensor:
+    """crow<true>() of attention.hip: min(row, N - 1)."""
+    return rows.clamp(max=n - 1)
+
+
+def flash_attn_fwd_padded(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    causal: bool = True,
+    scale: Optional[float] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """attn_fwd_kernel<true>: 128-row blocks of 4 waves, each wave two
+    16-row sub-tiles, full 64-key tiles, log2-domain online softmax."""
+    N, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale2 = scale * _LOG2E
+    qf, kf, vf = q.float(), k.float(), v.float()
+    # poisoned outputs: a store the predicate should have made shows as NaN
+    o = torch.full((N, D), float('nan'))
+    lse = torch.full((N,), float('nan'))
+
+    nqb = (N + 127) // 128
+    for qb0 in range(0, nqb * 128, 128):
+        kv_end_block = min(qb0 + 128, N) if causal else N
+        ntiles = (kv_end_block + 63) // 64
+        for wave in range(4):
+            i0 = qb0 + 32 * wave
+            if not i0 < N:  # `valid`
+                continue
+            my_kv_end = i0 + 32 if causal else N
+            for sub in range(2):
+                qi0 = i0 + 16 * sub
+                q_g = qi0 + torch.arange(16)
+                qrows = qf[_crow(q_g, N)]
+                m_run = torch.full((16,), _NEG)
+                s_run = torch.zeros(16)
+                acc = torch.zeros(16, D)
+                for jt in range(ntiles):
+                    j0 = jt * 64
+                    if not j0 < my_kv_end:
+                        continue
+                    if causal and j0 >= qi0 + 16:
+                        continue  # tile fully past the diagonal
+                    key_g = j0 + torch.arange(64)
+                    krows = kf[_crow(key_g, N)]
+                    vrows = vf[_crow(key_g, N)]
+                    s = (qrows @ krows.T) * scale2  # [16 q, 64 keys], log2 domain
+                    if causal:
+                        s = s.masked_fill(key_g.unsqueeze(0) > q_g.unsqueeze(1), _NEG)
+                    s = s.masked_fill((key_g >= N).unsqueeze(0), _NEG)
+                    m_new = torch.maximum(m_run, s.max(dim=1).values)
+                    alpha = torch.exp2(m_run - m_new)
+                    p = torch.exp2(s - m_new.unsqueeze(1))
+                    s_run = s_run * alpha + p.sum(dim=1)
+                    m_run = m_new
+                    acc = acc * alpha.unsqueeze(1) + p @ vrows
+                keep = q_g < N  # per-row store predicate
+                o[q_g[keep]] = (acc / s_run.unsqueeze(1))[keep]
+                lse[q_g[keep]] = (0.69314718 * m_run + torch.log(s_run))[keep]
+    return o, lse
+
+
+def flash_attn_bwd_padded(
+    do: torch.Tensor,
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    o: torch.Tensor,
+    lse: torch.Tensor,
+    causal: bool = True,
+    scale: Optional[float] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """attn_bwd_delta_kernel + attn_bwd_dkdv_kernel<true> +
+    attn_bwd_dq_kernel<true>."""
+    N, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale2 = scale * _LOG2E
+    qf, kf, vf, dof, of = (t.float() for t in (q, k, v, do, o))
+    lse2 = lse.float() * _LOG2E
+
+    # delta: one row at a time over the N real rows, nothing to clamp
+    delta = (dof * of).sum(dim=1)
+
+    dq = torch.full((N, D), float('nan'))
+    dk = torch.full((N, D), float('nan'))
+    dv = torch.full((N, D), float('nan'))
+
+    def p_and_ds(q_g, key_g):
+        """Recomputed P and dS for one [16 q, 16 keys] pair of clamped tiles."""
+        qr, kr = _crow(q_g, N), _crow(key_g, N)
+        s2 = (qf[qr] @ kf[kr].T) * scale2
+        dp = dof[qr] @ vf[kr].T
+        live = (key_g < N).unsqueeze(0) & (q_g < N).unsqueeze(1)
+        if causal:
+            live = live & (key_g.unsqueeze(0) <= q_g.unsqueeze(1))
+        p = torch.where(live, torch.exp2(s2 - lse2[qr].unsqueeze(1)), torch.zeros(()))
+        ds = p * (dp - delta[qr].unsqueeze(1)) * scale
+        return p, ds
+
+    # ---- dK / dV: 64-key blocks of 4 waves x 16 keys, 32-row q steps ----
+    nkb = (N + 63) // 64
+    for kb0 in range(0, nkb * 64, 64):
+        i_start = (kb0 & ~31) if causal else 0
+        for wave in range(4):
+            j0 = kb0 + 16 * wave
+            if not j0 < N:  # `valid`
+                continue
+            key_g = j0 + torch.arange(16)
+            dv_acc = torch.zeros(16, D)
+            dk_acc = torch.zeros(16, D)
+            for i0 in range(i_start, N, 32):
+                if causal and not i0 + 32 > j0:
+                    continue
+                for hq in range(2):
+                    q_g = i0 + 16 * hq + torch.arange(16)
+                    p, ds = p_and_ds(q_g, key_g)
+                    dv_acc += p.T @ dof[_crow(q_g, N)]
+                    dk_acc += ds.T @ qf[_crow(q_g, N)]
+            keep = key_g < N
+            dv[key_g[keep]] = dv_acc[keep]
+            dk[key_g[keep]] = dk_acc[keep]
+
+    # ---- dQ: 64-row blocks of 4 waves x 16 q rows, 32-key tiles ----
+    nqb = (N + 63) // 64
+    for qb0 in range(0, nqb * 64, 64):
+        kv_end_block = min(qb0 + 64, N) if causal else N
+        for wave in range(4):
+            i0 = qb0 + 16 * wave
+            if not i0 < N:  # `valid`
+                continue
+            my_kv_end = i0 + 16 if causal else N
+            q_g = i0 + torch.arange(16)
+            dq_acc = torch.zeros(16, D)
+            for j0 in range(0, kv_end_block, 32):
+                if not j0 < my_kv_end:
+                    continue
+                for h in range(2):
+                    key_g = j0 + 16 * h + torch.arange(16)
+                    _, ds = p_and_ds(q_g, key_g)
+                    dq_acc += ds @ kf[_crow(key_g, N)]
+            keep = q_g < N
+            dq[q_g[keep]] = dq_acc[keep]
+    return dq, dk, dv
+
+
 def mha_fwd_tiled(q, k, v, causal=True, bq=32, bk=64):
     """[B, H, N, D] wrapper over the per-slice tile algorithm."""
     B, H, N, D = q.shape

@@ -74,10 +74,27 @@ __device__ __forceinline__ const __hip_bfloat16* tslice(const __hip_bfloat16* t,
   return t + (int64_t)(bh / H) * st.b + (int64_t)(bh % H) * st.h;
 }
 
+// Ragged sequence lengths (N % 64 != 0): every kernel below takes a
+// `kRagged` template flag. <false> is the aligned code, unchanged; <true>
+// adds three things and nothing else:
+//   * every global ROW index goes through crow(): min(row, N - 1). A tile
+//     that hangs over the end of the sequence re-reads the last real row,
+//     so no load can leave the tensor and the duplicates are finite data;
+//   * the duplicates are masked out of the math (fwd: score = -1e30 for
+//     key >= N; bwd: p = 0 for key >= N or q >= N, so dS = 0 * finite);
+//   * every global store is predicated per row on row < N.
+// Loop bounds need no change: they already round up to whole tiles.
+template <bool kRagged>
+__device__ __forceinline__ int crow(int row, int N) {
+  if constexpr (kRagged) return min(row, N - 1);
+  return row;
+}
+
 // Occupancy note: 204 VGPRs + 32 AGPRs -> 2 waves/SIMD. Forcing 3
 // waves/SIMD via amdgpu_waves_per_eu(3) spills 164 B/lane and measured
 // SLOWER (552 vs 508 us causal at the GPT-2 shape) — the spill traffic
 // in the inner loop outweighs the extra latency hiding. Keep 2 waves.
+template <bool kRagged>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
@@ -126,8 +143,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
       for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          qf[sub][c] = *(const bf16x8*)(qp + (int64_t)(i0 + 16 * sub + row16) * sq.r + 32 * c +
-                                        8 * grp);
+          qf[sub][c] =
+              *(const bf16x8*)(qp + (int64_t)crow<kRagged>(i0 + 16 * sub + row16, N) * sq.r +
+                               32 * c + 8 * grp);
         }
       }
     }
@@ -141,18 +159,30 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
 #pragma unroll
       for (int db = 0; db < 4; ++db) o_acc[sub][db] = f32x4{0, 0, 0, 0};
 
+    // Ragged N: kv_end_block <= N is the number of KEYS the block needs
+    // and ntiles rounds it up to whole 64-key tiles, so the last tile may
+    // cover keys >= N (clamped loads, masked scores). Causal diagonal: a
+    // stored row q < N of this wave (i0 <= q < i0 + 32) needs keys 0..q.
+    // Key q sits in the tile with j0 = 64 * (q / 64) <= q, and
+    // q < min(qb0 + 128, N) = kv_end_block gives q / 64 < ntiles, while
+    // j0 <= q < i0 + 32 = my_kv_end, so that tile is walked and not
+    // skipped. Rows q >= N of a partly valid wave tile compute on clamped
+    // data and are never stored. Key 0 < N is in tile 0, which every
+    // sub-tile visits, so m_run is finite after the first tile.
     const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
     const int my_kv_end = causal ? (i0 + 2 * kQT) : N;
 
     // write-late double buffer (guide §6 G15): the NEXT tile's global
     // loads stay in flight through the current tile's compute; their
     // ds_write targets the other buffer just before the single barrier.
-    *(bf16x8*)(&k_lds[0][st_row][st_col]) = *(const bf16x8*)(kp + (int64_t)st_row * sk.r + st_col);
+    *(bf16x8*)(&k_lds[0][st_row][st_col]) =
+        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(st_row, N) * sk.r + st_col);
     *(bf16x8*)(&k_lds[0][st_row + 32][st_col]) =
-        *(const bf16x8*)(kp + (int64_t)(st_row + 32) * sk.r + st_col);
-    *(bf16x8*)(&v_tr[0][st_vt]) = *(const bf16x8*)(vp + (int64_t)st_row * sv.r + st_col);
+        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(st_row + 32, N) * sk.r + st_col);
+    *(bf16x8*)(&v_tr[0][st_vt]) =
+        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(st_row, N) * sv.r + st_col);
     *(bf16x8*)(&v_tr[0][2048 + st_vt]) =
-        *(const bf16x8*)(vp + (int64_t)(st_row + 32) * sv.r + st_col);
+        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(st_row + 32, N) * sv.r + st_col);
     __syncthreads();
 
     const int ntiles = (kv_end_block + kKTF - 1) / kKTF;
@@ -162,10 +192,14 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
       bf16x8 knext0, knext1, vnext0, vnext1;
       const bool has_next = jt + 1 < ntiles;
       if (has_next) {
-        knext0 = *(const bf16x8*)(kp + (int64_t)(j0 + kKTF + st_row) * sk.r + st_col);
-        knext1 = *(const bf16x8*)(kp + (int64_t)(j0 + kKTF + 32 + st_row) * sk.r + st_col);
-        vnext0 = *(const bf16x8*)(vp + (int64_t)(j0 + kKTF + st_row) * sv.r + st_col);
-        vnext1 = *(const bf16x8*)(vp + (int64_t)(j0 + kKTF + 32 + st_row) * sv.r + st_col);
+        knext0 = *(const bf16x8*)(kp + (int64_t)crow<kRagged>(j0 + kKTF + st_row, N) * sk.r +
+                                  st_col);
+        knext1 = *(const bf16x8*)(kp + (int64_t)crow<kRagged>(j0 + kKTF + 32 + st_row, N) * sk.r +
+                                  st_col);
+        vnext0 = *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j0 + kKTF + st_row, N) * sv.r +
+                                  st_col);
+        vnext1 = *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j0 + kKTF + 32 + st_row, N) * sv.r +
+                                  st_col);
       }
 
       if (valid && j0 < my_kv_end) {
@@ -211,6 +245,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
                 const int key_g = j0 + 16 * h + 4 * grp + r;
                 const int q_g = qi0 + row16;
                 if (key_g > q_g) s = -1e30f;
+              }
+              if constexpr (kRagged) {
+                if (j0 + 16 * h + 4 * grp + r >= N) s = -1e30f; // clamped duplicate key
               }
               sv[h * 4 + r] = s;
             }
@@ -283,11 +320,12 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
             const int q_o = 4 * grp + r;
             const float denom = __shfl(s_run[sub], q_o, kWave);
             const float val = o_acc[sub][db][r] / denom;
-            o[(int64_t)bh * N * kAttnD + (int64_t)(i0 + 16 * sub + q_o) * kAttnD + 16 * db +
-              row16] = __float2bfloat16(val);
+            if (!kRagged || i0 + 16 * sub + q_o < N)
+              o[(int64_t)bh * N * kAttnD + (int64_t)(i0 + 16 * sub + q_o) * kAttnD + 16 * db +
+                row16] = __float2bfloat16(val);
           }
         }
-        if (lane < 16) {
+        if (lane < 16 && (!kRagged || i0 + 16 * sub + row16 < N)) {
           // convert the log2-domain stats back to natural-log lse
           lse[(int64_t)bh * N + i0 + 16 * sub + row16] =
               0.69314718f * m_run[sub] + __logf(s_run[sub]);
@@ -311,7 +349,7 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
   TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
               "k/v must be bf16");
   const int B = q.size(0), H = q.size(1), N = q.size(2);
-  TORCH_CHECK(N % kKTF == 0, "N must be a multiple of 64");
+  TORCH_CHECK(N >= 1, "N must be at least 1");
   TORCH_CHECK(o.is_contiguous() && o.sizes() == q.sizes(), "o must be contiguous [B,H,N,D]");
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() >= (int64_t)B * H * N,
               "lse must be fp32[B*H*N]");
@@ -320,7 +358,10 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
   const int64_t total_blocks = (int64_t)BH * ((N + qrows_per_block - 1) / qrows_per_block);
   const int blocks = (int)std::min<int64_t>(total_blocks, kMaxGrid);
   auto stream = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
+  // aligned N keeps the unmasked instruction stream; anything else takes
+  // the clamped/masked/predicated instantiation
+  auto kernel = (N % kKTF == 0) ? attn_fwd_kernel<false> : attn_fwd_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
                      (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
                      (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
                      lse.data_ptr<float>(), BH, H, N, (float)scale, causal, strides_of(q),
@@ -345,6 +386,9 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
 // exactly like the forward's P.
 
 // -------------------------------------------------- delta = rowsum(dO*O)
+// Per-row kernel: r0 runs over the BH * N real rows only and every load
+// and the store index with r0 (or its (bh, rr) split, rr < N), so it is
+// correct for any N as it stands and needs no ragged variant.
 __global__ void __launch_bounds__(kBlock) attn_bwd_delta_kernel(
     const __hip_bfloat16* __restrict__ dout, const __hip_bfloat16* __restrict__ o,
     float* __restrict__ delta, int64_t rows, int H, int N, Strides sdo) {
@@ -370,6 +414,7 @@ __global__ void __launch_bounds__(kBlock) attn_bwd_delta_kernel(
 // Block = 4 waves, each owning a 16-key tile of one (b,h); q-tiles of 32
 // rows (Q and dO staged in shared LDS) stream past. Per q-tile, per wave:
 // 2 MFMAs S^T, 2 MFMAs dP^T, 4+4 MFMAs dV/dK accumulation (k = 32 q rows).
+template <bool kRagged>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
@@ -414,8 +459,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     if (valid) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        kf[c] = *(const bf16x8*)(kp + (int64_t)(j0 + row16) * sk.r + 32 * c + 8 * grp);
-        vf2[c] = *(const bf16x8*)(vp + (int64_t)(j0 + row16) * sv.r + 32 * c + 8 * grp);
+        const int kr = crow<kRagged>(j0 + row16, N);
+        kf[c] = *(const bf16x8*)(kp + (int64_t)kr * sk.r + 32 * c + 8 * grp);
+        vf2[c] = *(const bf16x8*)(vp + (int64_t)kr * sv.r + 32 * c + 8 * grp);
       }
     }
 
@@ -426,12 +472,22 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
       dk_acc[db] = f32x4{0, 0, 0, 0};
     }
 
+    // Ragged N: nkb rounds the key blocks up, so the last block's waves
+    // may own keys >= N (clamped loads, p = 0, no store), and the q loop
+    // walks 32-row steps while i0 < N, so the last step may cover q rows
+    // >= N (clamped loads, p = 0: a padded query adds nothing to dK/dV).
+    // Causal diagonal: a stored key j < N of this block needs q rows
+    // j..N-1. kb0 is a multiple of 64, so i_start = kb0 <= j, and the
+    // steps from kb0 to the one holding N - 1 cover every q in [j, N);
+    // the per-wave skip only drops steps with i0 + 32 <= j0, i.e. whose
+    // q rows are all below every key of the wave.
     const int i_start = causal ? (kb0 & ~(kQStep - 1)) : 0; // block-aligned diag
     for (int i0 = i_start; i0 < N; i0 += kQStep) {
       // ---- stage Q and dO into tiled images (one bf16x8 per thread) ----
       const int st_t = vt_idx(st_row, st_col);
-      *(bf16x8*)(&q_lds[st_t]) = *(const bf16x8*)(qp + (int64_t)(i0 + st_row) * sq.r + st_col);
-      *(bf16x8*)(&do_lds[st_t]) = *(const bf16x8*)(dop + (int64_t)(i0 + st_row) * sdo.r + st_col);
+      const int st_g = crow<kRagged>(i0 + st_row, N);
+      *(bf16x8*)(&q_lds[st_t]) = *(const bf16x8*)(qp + (int64_t)st_g * sq.r + st_col);
+      *(bf16x8*)(&do_lds[st_t]) = *(const bf16x8*)(dop + (int64_t)st_g * sdo.r + st_col);
       __syncthreads();
 
       if (valid && (!causal || i0 + kQStep > j0)) {
@@ -439,8 +495,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
 #pragma unroll
         for (int hq = 0; hq < 2; ++hq) {
           const int q0 = i0 + 16 * hq; // this half's first q row
-          const float lse2_q = lsep[q0 + row16] * 1.44269504f; // log2 domain
-          const float del_q = delp[q0 + row16];
+          const int qr = crow<kRagged>(q0 + row16, N);
+          const float lse2_q = lsep[qr] * 1.44269504f; // log2 domain
+          const float del_q = delp[qr];
 
           // ---- S^T = K Q^T (rows = key, cols = q) ----
           f32x4 acc = {0, 0, 0, 0};
@@ -461,7 +518,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
             const int key_g = j0 + 4 * grp + r;
             const int q_g = q0 + row16;
             float p = 0.0f;
-            if (!causal || key_g <= q_g) {
+            if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
               p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
             }
             const float ds = p * (dpt[r] - del_q) * scale;
@@ -502,6 +559,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key_o = 4 * grp + r;
+          if (kRagged && j0 + key_o >= N) continue;
           dv[(int64_t)bh * N * kAttnD + (int64_t)(j0 + key_o) * kAttnD + 16 * db + row16] =
               __float2bfloat16(dv_acc[db][r]);
           dk[(int64_t)bh * N * kAttnD + (int64_t)(j0 + key_o) * kAttnD + 16 * db + row16] =
@@ -515,6 +573,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
 // ------------------------------------------------------------------- dQ
 // Mirror of the forward: block = 4 waves x one 16-q tile; 32-key KV tiles
 // (K and V staged shared). dq[q][d] += dS[q][key] @ K[key][d].
+template <bool kRagged>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
@@ -555,25 +614,32 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
     if (valid) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        qf[c] = *(const bf16x8*)(qp + (int64_t)(i0 + row16) * sq.r + 32 * c + 8 * grp);
-        dof[c] = *(const bf16x8*)(dop + (int64_t)(i0 + row16) * sdo.r + 32 * c + 8 * grp);
+        const int qr = crow<kRagged>(i0 + row16, N);
+        qf[c] = *(const bf16x8*)(qp + (int64_t)qr * sq.r + 32 * c + 8 * grp);
+        dof[c] = *(const bf16x8*)(dop + (int64_t)qr * sdo.r + 32 * c + 8 * grp);
       }
-      lse_q = lsep[i0 + row16] * 1.44269504f; // log2 domain
-      del_q = delp[i0 + row16];
+      lse_q = lsep[crow<kRagged>(i0 + row16, N)] * 1.44269504f; // log2 domain
+      del_q = delp[crow<kRagged>(i0 + row16, N)];
     }
 
     f32x4 dq_acc[4];
 #pragma unroll
     for (int db = 0; db < 4; ++db) dq_acc[db] = f32x4{0, 0, 0, 0};
 
+    // Ragged N: the key loop walks 32-key tiles while j0 < kv_end_block
+    // <= N, so only the last tile can cover keys >= N (clamped loads,
+    // p = 0). Causal diagonal: a stored row q < N of this wave
+    // (i0 <= q < i0 + 16) needs keys 0..q; key q sits in the tile with
+    // j0 = 32 * (q / 32) <= q < min(qb0 + 64, N) = kv_end_block, and
+    // j0 <= q < i0 + 16 = my_kv_end, so it is walked and not skipped.
     const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
     const int my_kv_end = causal ? (i0 + kQT) : N;
 
     for (int j0 = 0; j0 < kv_end_block; j0 += kKT) {
+      const int st_g = crow<kRagged>(j0 + st_row, N);
       *(bf16x8*)(&k_lds[vt_idx(st_row, st_col)]) =
-          *(const bf16x8*)(kp + (int64_t)(j0 + st_row) * sk.r + st_col);
-      *(bf16x8*)(&v_lds[st_row][st_col]) =
-          *(const bf16x8*)(vp + (int64_t)(j0 + st_row) * sv.r + st_col);
+          *(const bf16x8*)(kp + (int64_t)st_g * sk.r + st_col);
+      *(bf16x8*)(&v_lds[st_row][st_col]) = *(const bf16x8*)(vp + (int64_t)st_g * sv.r + st_col);
       __syncthreads();
 
       if (valid && j0 < my_kv_end) {
@@ -596,7 +662,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
             const int key_g = j0 + 16 * h + 4 * grp + r;
             const int q_g = i0 + row16;
             float p = 0.0f;
-            if (!causal || key_g <= q_g) {
+            if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
               p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q); // lse_q in log2 domain
             }
             dsw[r] = (__bf16)(p * (dpt[r] - del_q) * scale);
@@ -629,6 +695,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int q_o = 4 * grp + r;
+          if (kRagged && i0 + q_o >= N) continue;
           dq[(int64_t)bh * N * kAttnD + (int64_t)(i0 + q_o) * kAttnD + 16 * db + row16] =
               __float2bfloat16(dq_acc[db][r]);
         }
@@ -651,7 +718,7 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
   TORCH_CHECK(dq.sizes() == q.sizes() && dk.sizes() == q.sizes() && dv.sizes() == q.sizes(),
               "grad output shapes must equal q");
   const int B = q.size(0), H = q.size(1), N = q.size(2);
-  TORCH_CHECK(N % 64 == 0, "bwd requires N to be a multiple of 64");
+  TORCH_CHECK(N >= 1, "N must be at least 1");
   const int BH = B * H;
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() >= (int64_t)BH * N,
               "lse must be fp32[BH*N]");
@@ -666,7 +733,10 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
                      strides_of(dout));
 
   const int64_t kv_blocks = (int64_t)BH * ((N + 63) / 64);
-  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3((int)std::min<int64_t>(kv_blocks, kMaxGrid)),
+  const bool ragged = N % 64 != 0; // see crow(): <false> is the aligned code
+  auto dkdv_kernel = ragged ? attn_bwd_dkdv_kernel<true> : attn_bwd_dkdv_kernel<false>;
+  auto dq_kernel = ragged ? attn_bwd_dq_kernel<true> : attn_bwd_dq_kernel<false>;
+  hipLaunchKernelGGL(dkdv_kernel, dim3((int)std::min<int64_t>(kv_blocks, kMaxGrid)),
                      dim3(kWavesPerBlock * kWave), 0, stream,
                      (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
                      (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
@@ -676,7 +746,7 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
                      strides_of(dout));
 
   const int64_t q_blocks = (int64_t)BH * ((N + 63) / 64);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((int)std::min<int64_t>(q_blocks, kMaxGrid)),
+  hipLaunchKernelGGL(dq_kernel, dim3((int)std::min<int64_t>(q_blocks, kMaxGrid)),
                      dim3(kWavesPerBlock * kWave), 0, stream,
                      (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
                      (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),

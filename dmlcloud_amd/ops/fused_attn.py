@@ -2,12 +2,16 @@
 
 `sdpa(q, k, v, causal=True)` matches
 F.scaled_dot_product_attention(..., is_causal=causal) for bf16
-[B, H, N, 64] self-attention device tensors; anything else (other head
-dims, cross-attention geometry, non-bf16) falls back to torch SDPA
-(AOTriton). The fused path is ON by default whenever usable — set
+[B, H, N, 64] self-attention device tensors of ANY sequence length
+N >= 1: a multiple of 64 runs the aligned kernels, every other length
+their ragged instantiation (clamped loads, masked tail, predicated
+stores — ops/csrc/attention.hip). Anything else (other head dims,
+cross-attention geometry, non-bf16) falls back to torch SDPA
+(AOTriton); `fused_attention_usable(q, k, v)` tells which path a call
+takes. The fused path is ON by default whenever usable — set
 DMLCLOUD_DISABLE_FUSED_ATTN=1 to force the AOTriton path (the A/B
 ladder in profiles/ uses this switch). Numerics are verified in
-tests/test_gpu.py.
+tests/test_gpu.py and tests/test_gpu_attention_ragged.py.
 """
 
 import math
@@ -57,7 +61,7 @@ def _usable(q, k, v):
         and q.dtype == torch.bfloat16
         and q.dim() == 4
         and q.shape[-1] == 64
-        and q.shape[-2] % 64 == 0
+        and q.shape[-2] >= 1
         and k.shape == q.shape
         and v.shape == q.shape
         and k.dtype == q.dtype
@@ -65,6 +69,14 @@ def _usable(q, k, v):
         and k.device == q.device
         and v.device == q.device
     )
+
+
+def fused_attention_usable(q, k, v) -> bool:
+    """True when `sdpa(q, k, v)` will run the native MFMA kernels, False
+    when it will fall back to torch SDPA: exactly the decision `sdpa`
+    makes (bf16 device tensors, [B, H, N, 64] with any N >= 1, k and v
+    shaped like q, extension built, no DMLCLOUD_DISABLE_FUSED_ATTN)."""
+    return bool(_usable(q, k, v))
 
 
 def _lastdim_ok(t):

@@ -1,4 +1,5 @@
-"""Micro-benchmark: experimental MFMA attention forward vs SDPA (AOTriton)."""
+"""Micro-benchmark: MFMA attention forward/backward vs SDPA (AOTriton),
+aligned shapes plus one ragged sequence length (N=1000)."""
 
 import math
 import os
@@ -85,3 +86,7 @@ if __name__ == '__main__':
     bench_bwd(64, 12, 1024)
     bench_bwd(64, 12, 1024, causal=False)
     bench_bwd(16, 16, 2048)
+    # ragged N (not a multiple of 64): the kRagged kernel instantiations
+    # walk exactly the tiles of the N=1024 rows above; sdpa beside each
+    bench(64, 12, 1000)
+    bench_bwd(64, 12, 1000)
