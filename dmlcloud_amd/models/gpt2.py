@@ -1,9 +1,15 @@
 """GPT-2 small for the synthetic-token benchmark config (BASELINE.json).
 
 Self-contained GPT-2 (124M): learned positional embeddings, pre-LN
-blocks, GELU MLP, tied LM head. Attention uses
-torch.nn.functional.scaled_dot_product_attention, which lowers to AOTriton
-flash kernels on ROCm.
+blocks, GELU MLP, tied LM head. Attention goes through
+ops.fused_attn.sdpa: the project's MFMA flash-attention kernels for bf16
+device tensors with head dim 64 (GPT-2 small), torch SDPA otherwise.
+
+Packed sequences: `GPT2.forward(idx, targets, doc_ids=...)` takes an
+integer [B, T] tensor whose runs of equal values are the documents packed
+into each row. Attention then stays inside a document and the learned
+positions restart at every document start, so each document is computed
+exactly as if it were alone in its row.
 """
 
 import math
@@ -13,7 +19,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..ops.fused_attn import sdpa
+from ..ops.fused_attn import document_starts, sdpa
 from ..ops.fused_ln import LayerNorm
 from ..ops.fused_loss import cross_entropy
 
@@ -36,7 +42,7 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
-    def forward(self, x):
+    def forward(self, x, doc_start=None):
         B, T, C = x.shape
         qkv = self.c_attn(x)
         q, k, v = qkv.split(C, dim=2)
@@ -46,7 +52,7 @@ class CausalSelfAttention(nn.Module):
         # custom MFMA flash attention on bf16/D=64 (ops/fused_attn.py);
         # beats AOTriton fwd+bwd combined at this shape — falls back to
         # torch SDPA otherwise
-        y = sdpa(q, k, v, causal=True)
+        y = sdpa(q, k, v, causal=True) if doc_start is None else sdpa(q, k, v, causal=True, doc_start=doc_start)
         y = y.transpose(1, 2).reshape(B, T, C)
         return self.c_proj(y)
 
@@ -63,8 +69,8 @@ class Block(nn.Module):
             nn.Linear(4 * cfg.n_embd, cfg.n_embd),
         )
 
-    def forward(self, x):
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x, doc_start=None):
+        x = x + self.attn(self.ln_1(x), doc_start)
         x = x + self.mlp(self.ln_2(x))
         return x
 
@@ -96,12 +102,19 @@ class GPT2(nn.Module):
         elif isinstance(module, nn.Embedding):
             nn.init.normal_(module.weight, mean=0.0, std=0.02)
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, doc_ids=None):
         B, T = idx.shape
         pos = torch.arange(T, device=idx.device)
+        doc_start = None
+        if doc_ids is not None:
+            # once per step, on the device, no sync; positions restart at
+            # each document (a document longer than the table reuses the
+            # last position instead of indexing past it)
+            doc_start = document_starts(doc_ids)
+            pos = (pos - doc_start).clamp(max=self.cfg.n_positions - 1)
         x = self.wte(idx) + self.wpe(pos)
         for block in self.blocks:
-            x = block(x)
+            x = block(x, doc_start)
         x = self.ln_f(x)
         logits = self.lm_head(x)
         if targets is None:

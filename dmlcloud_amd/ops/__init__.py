@@ -221,3 +221,17 @@ def clip_grad_norm_(flat: torch.Tensor, max_norm: float, norm_scale: float = 1.0
     norm = ref.l2_norm(flat) * norm_scale
     ref.clip_by_norm_(flat, norm[0], max_norm)
     return norm
+
+
+# ------------------------------------------------------------------ attention
+
+# at the end: fused_attn imports _C and is_available from this module
+from .fused_attn import (  # noqa: E402,F401
+    check_document_starts,
+    document_mask,
+    document_starts,
+    document_starts_from_eos,
+    fused_attention_enabled,
+    fused_attention_usable,
+    sdpa,
+)

@@ -125,16 +125,39 @@ def _crow(rows: torch.Tensor, n: int) -> torch.Tensor:
     return rows.clamp(max=n - 1)
 
 
+def _dstart(doc_start: torch.Tensor, rows: torch.Tensor, n: int) -> torch.Tensor:
+    """dstart() of attention.hip: the value read for row r = min(row,
+    N - 1), clamped to [0, r]."""
+    r = rows.clamp(max=n - 1)
+    return torch.minimum(doc_start.long()[r].clamp(min=0), r)
+
+
+def _dstart1(doc_start: torch.Tensor, row: int, n: int) -> int:
+    return int(_dstart(doc_start, torch.tensor([row]), n)[0])
+
+
+# Packed sequences: both functions below take an optional per-slice
+# `doc_start[N]` (see ops/fused_attn.py for the semantics) and then emulate
+# the kernels' <kDoc = true> instantiations: the same clamp, the same
+# masks, the same block / wave tile skips and the dkdv break. Fully masked
+# tiles of a straddling sub-tile are walked, not special-cased, so the
+# -1e30 "wipe" (alpha = exp2(-1e30 - m) = 0 at the first valid tile) is
+# what makes the result right here exactly as on the device. With
+# doc_start=None not one operation changes.
+
+
 def flash_attn_fwd_padded(
     q: torch.Tensor,
     k: torch.Tensor,
     v: torch.Tensor,
     causal: bool = True,
     scale: Optional[float] = None,
+    doc_start: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """attn_fwd_kernel<true>: 128-row blocks of 4 waves, each wave two
     16-row sub-tiles, full 64-key tiles, log2-domain online softmax."""
     N, D = q.shape
+    assert doc_start is None or causal, 'doc_start requires causal attention'
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     scale2 = scale * _LOG2E
     qf, kf, vf = q.float(), k.float(), v.float()
@@ -146,6 +169,8 @@ def flash_attn_fwd_padded(
     for qb0 in range(0, nqb * 128, 128):
         kv_end_block = min(qb0 + 128, N) if causal else N
         ntiles = (kv_end_block + 63) // 64
+        # block-level skip: the walk begins at the tile holding start[qb0]
+        jt_begin = 0 if doc_start is None else _dstart1(doc_start, qb0, N) // 64
         for wave in range(4):
             i0 = qb0 + 32 * wave
             if not i0 < N:  # `valid`
@@ -155,22 +180,33 @@ def flash_attn_fwd_padded(
                 qi0 = i0 + 16 * sub
                 q_g = qi0 + torch.arange(16)
                 qrows = qf[_crow(q_g, N)]
+                if doc_start is not None:
+                    q_start = _dstart(doc_start, q_g, N)
+                    q_last = _crow(q_g, N)  # min(q, N - 1): causal and ragged end
+                    sub_start = _dstart1(doc_start, qi0, N)
                 m_run = torch.full((16,), _NEG)
                 s_run = torch.zeros(16)
                 acc = torch.zeros(16, D)
-                for jt in range(ntiles):
+                for jt in range(jt_begin, ntiles):
                     j0 = jt * 64
                     if not j0 < my_kv_end:
                         continue
                     if causal and j0 >= qi0 + 16:
                         continue  # tile fully past the diagonal
+                    if doc_start is not None and j0 + 64 <= sub_start:
+                        continue  # tile wholly in earlier documents
                     key_g = j0 + torch.arange(64)
                     krows = kf[_crow(key_g, N)]
                     vrows = vf[_crow(key_g, N)]
                     s = (qrows @ krows.T) * scale2  # [16 q, 64 keys], log2 domain
-                    if causal:
-                        s = s.masked_fill(key_g.unsqueeze(0) > q_g.unsqueeze(1), _NEG)
-                    s = s.masked_fill((key_g >= N).unsqueeze(0), _NEG)
+                    if doc_start is not None:
+                        # one range test: start[q] <= key <= min(q, N - 1)
+                        dead = (key_g.unsqueeze(0) < q_start.unsqueeze(1)) | (key_g.unsqueeze(0) > q_last.unsqueeze(1))
+                        s = s.masked_fill(dead, _NEG)
+                    else:
+                        if causal:
+                            s = s.masked_fill(key_g.unsqueeze(0) > q_g.unsqueeze(1), _NEG)
+                        s = s.masked_fill((key_g >= N).unsqueeze(0), _NEG)
                     m_new = torch.maximum(m_run, s.max(dim=1).values)
                     alpha = torch.exp2(m_run - m_new)
                     p = torch.exp2(s - m_new.unsqueeze(1))
@@ -192,10 +228,12 @@ def flash_attn_bwd_padded(
     lse: torch.Tensor,
     causal: bool = True,
     scale: Optional[float] = None,
+    doc_start: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """attn_bwd_delta_kernel + attn_bwd_dkdv_kernel<true> +
     attn_bwd_dq_kernel<true>."""
     N, D = q.shape
+    assert doc_start is None or causal, 'doc_start requires causal attention'
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     scale2 = scale * _LOG2E
     qf, kf, vf, dof, of = (t.float() for t in (q, k, v, do, o))
@@ -216,6 +254,8 @@ def flash_attn_bwd_padded(
         live = (key_g < N).unsqueeze(0) & (q_g < N).unsqueeze(1)
         if causal:
             live = live & (key_g.unsqueeze(0) <= q_g.unsqueeze(1))
+        if doc_start is not None:  # p = 0 for key < start[q]
+            live = live & (key_g.unsqueeze(0) >= _dstart(doc_start, q_g, N).unsqueeze(1))
         p = torch.where(live, torch.exp2(s2 - lse2[qr].unsqueeze(1)), torch.zeros(()))
         ds = p * (dp - delta[qr].unsqueeze(1)) * scale
         return p, ds
@@ -224,6 +264,14 @@ def flash_attn_bwd_padded(
     nkb = (N + 63) // 64
     for kb0 in range(0, nkb * 64, 64):
         i_start = (kb0 & ~31) if causal else 0
+        # the block-uniform break: the first q-step whose first row starts
+        # behind the block's last key ends the walk for all four waves
+        i_stop = N
+        if doc_start is not None:
+            for i0 in range(i_start, N, 32):
+                if _dstart1(doc_start, i0, N) > kb0 + 63:
+                    i_stop = i0
+                    break
         for wave in range(4):
             j0 = kb0 + 16 * wave
             if not j0 < N:  # `valid`
@@ -231,7 +279,7 @@ def flash_attn_bwd_padded(
             key_g = j0 + torch.arange(16)
             dv_acc = torch.zeros(16, D)
             dk_acc = torch.zeros(16, D)
-            for i0 in range(i_start, N, 32):
+            for i0 in range(i_start, i_stop, 32):
                 if causal and not i0 + 32 > j0:
                     continue
                 for hq in range(2):
@@ -247,16 +295,21 @@ def flash_attn_bwd_padded(
     nqb = (N + 63) // 64
     for qb0 in range(0, nqb * 64, 64):
         kv_end_block = min(qb0 + 64, N) if causal else N
+        # block-level skip: the walk begins at the 32-key tile holding start[qb0]
+        j_begin = 0 if doc_start is None else _dstart1(doc_start, qb0, N) & ~31
         for wave in range(4):
             i0 = qb0 + 16 * wave
             if not i0 < N:  # `valid`
                 continue
             my_kv_end = i0 + 16 if causal else N
             q_g = i0 + torch.arange(16)
+            wave_start = 0 if doc_start is None else _dstart1(doc_start, i0, N)
             dq_acc = torch.zeros(16, D)
-            for j0 in range(0, kv_end_block, 32):
+            for j0 in range(j_begin, kv_end_block, 32):
                 if not j0 < my_kv_end:
                     continue
+                if not j0 + 32 > wave_start:
+                    continue  # tile wholly in earlier documents
                 for h in range(2):
                     key_g = j0 + 16 * h + torch.arange(16)
                     _, ds = p_and_ds(q_g, key_g)

@@ -90,16 +90,50 @@ __device__ __forceinline__ int crow(int row, int N) {
   return row;
 }
 
+// Packed sequences (document mask): every kernel below also takes a
+// `kDoc` template flag and an int32 `doc_start[B, N]` (shared by all
+// heads). doc_start[b][i] is the index of the first token of the
+// document token i belongs to; with causal attention query i attends
+// keys doc_start[b][i] <= j <= i, so the mask is ONE integer per query
+// row. <kDoc = false> is the code without it, unchanged. <true> adds:
+//   * dstart(): the value read for row q is clamped to [0, q], so
+//     whatever the tensor holds every row keeps its diagonal key and no
+//     index derived from it can leave [0, N);
+//   * the mask (fwd: score = -1e30 for key < start[q]; bwd: p = 0);
+//   * tile SKIPS derived from it, all block- or wave-uniform (the
+//     argument stands next to each loop).
+// The launchers require causal = true with a doc_start.
+// doc_start rides in the kernels' LAST stride argument, a
+// StridesDoc<kDoc>: plain Strides for <false>, Strides plus the pointer
+// for <true>. An argument of its own, even an empty struct, would move
+// the implicit kernel arguments behind it and with them one load offset
+// in the <false> kernels; this way their argument layout and instruction
+// stream are exactly what they were.
+template <bool kDoc>
+struct StridesDoc : Strides {
+  const int* doc_start;
+};
+template <>
+struct StridesDoc<false> : Strides {};
+
+// The row is clamped to N - 1 in every instantiation: an aligned N still
+// has 128-row forward blocks whose last waves lie wholly past N.
+__device__ __forceinline__ int dstart(const int* __restrict__ ds, int row, int N) {
+  const int r = min(row, N - 1);
+  return min(max(ds[r], 0), r);
+}
+
 // Occupancy note: 204 VGPRs + 32 AGPRs -> 2 waves/SIMD. Forcing 3
 // waves/SIMD via amdgpu_waves_per_eu(3) spills 164 B/lane and measured
 // SLOWER (552 vs 508 us causal at the GPT-2 shape) — the spill traffic
 // in the inner loop outweighs the extra latency hiding. Keep 2 waves.
-template <bool kRagged>
+template <bool kRagged, bool kDoc>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
-    float* __restrict__ lse, int BH, int H, int N, float scale, bool causal, Strides sq,
-    Strides sk, Strides sv) {
+    float* __restrict__ lse, int BH, int H, int N, float scale, bool causal_arg, Strides sq,
+    Strides sk, StridesDoc<kDoc> sv) {
+  const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStrideF];
   __shared__ __hip_bfloat16 k_lds[2][kKTF][kKVStride];
   // V lives in TILED images read by ds_read_b64_tr_b16 (empirically
@@ -172,21 +206,65 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
     const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
     const int my_kv_end = causal ? (i0 + 2 * kQT) : N;
 
+    // Documents (kDoc): row q attends keys start[q] <= key <= q, with
+    // start[q] = dstart(q) in [0, q]. A lane owns one query per sub-tile,
+    // so the mask is one register per sub-tile (q_start; q_span folds
+    // the causal and ragged upper end into the same test). Two skips:
+    //   * block: the walk begins at the tile holding start[qb0], tile
+    //     jt_begin. It depends on (bh, qb0) only, so the prologue, the
+    //     trip count and every __syncthreads() stay block-uniform. For a
+    //     well-formed doc_start the block's first row has the smallest
+    //     start, so no row loses a key. jt_begin <= qb0 / 64 < ntiles.
+    //   * sub-tile: tiles with j0 + 64 <= start[qi0] (sub_start, the
+    //     sub-tile's first row, wave-uniform) are skipped like the tiles
+    //     past the diagonal; the barriers sit outside that branch.
+    // Neither can skip a stored row's diagonal key q: its tile has
+    // j0 <= q, and start[qb0] <= qb0 <= q, start[qi0] <= qi0 <= q put it
+    // at or after both starting tiles. So whatever doc_start holds, every
+    // stored row sees at least one unmasked score (its diagonal).
+    // The wipe: a sub-tile that straddles a document boundary walks tiles
+    // that are fully masked for its later rows before their first valid
+    // key. On such a tile the row has m_run = -1e30 and every score
+    // -1e30, so m_new = -1e30, alpha = exp2(0) = 1 and every p =
+    // exp2(0) = 1: s_run grows by 64 and o_acc by a sum of 64 V rows per
+    // tile — garbage, but finite. At the row's first tile with a valid
+    // key m_new is a real score, alpha = exp2(-1e30 - m_new) = 0, and
+    // s_run * alpha, o_acc * alpha wipe the garbage to exactly 0 before
+    // the tile's own terms are added; the masked keys of that tile give
+    // p = exp2(-1e30 - m_new) = 0. The diagonal key guarantees that tile
+    // exists for every stored row.
+    int jt_begin = 0;
+    int q_start[2] = {0, 0};
+    unsigned q_span[2] = {0, 0}; // min(q, N - 1) - start[q] >= 0
+    int sub_start[2] = {0, 0};
+    if constexpr (kDoc) {
+      const int* dsp = sv.doc_start + (int64_t)(bh / H) * N;
+      jt_begin = dstart(dsp, qb0, N) / kKTF;
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        q_start[sub] = dstart(dsp, i0 + 16 * sub + row16, N);
+        q_span[sub] = (unsigned)(min(i0 + 16 * sub + row16, N - 1) - q_start[sub]);
+        sub_start[sub] = __builtin_amdgcn_readfirstlane(dstart(dsp, i0 + 16 * sub, N));
+      }
+    }
+    const int j_begin = jt_begin * kKTF;
+    const int buf0 = jt_begin & 1;
+
     // write-late double buffer (guide §6 G15): the NEXT tile's global
     // loads stay in flight through the current tile's compute; their
     // ds_write targets the other buffer just before the single barrier.
-    *(bf16x8*)(&k_lds[0][st_row][st_col]) =
-        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(st_row, N) * sk.r + st_col);
-    *(bf16x8*)(&k_lds[0][st_row + 32][st_col]) =
-        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(st_row + 32, N) * sk.r + st_col);
-    *(bf16x8*)(&v_tr[0][st_vt]) =
-        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(st_row, N) * sv.r + st_col);
-    *(bf16x8*)(&v_tr[0][2048 + st_vt]) =
-        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(st_row + 32, N) * sv.r + st_col);
+    *(bf16x8*)(&k_lds[buf0][st_row][st_col]) =
+        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(j_begin + st_row, N) * sk.r + st_col);
+    *(bf16x8*)(&k_lds[buf0][st_row + 32][st_col]) =
+        *(const bf16x8*)(kp + (int64_t)crow<kRagged>(j_begin + st_row + 32, N) * sk.r + st_col);
+    *(bf16x8*)(&v_tr[buf0][st_vt]) =
+        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j_begin + st_row, N) * sv.r + st_col);
+    *(bf16x8*)(&v_tr[buf0][2048 + st_vt]) =
+        *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j_begin + st_row + 32, N) * sv.r + st_col);
     __syncthreads();
 
     const int ntiles = (kv_end_block + kKTF - 1) / kKTF;
-    for (int jt = 0; jt < ntiles; ++jt) {
+    for (int jt = jt_begin; jt < ntiles; ++jt) {
       const int j0 = jt * kKTF;
       const int buf = jt & 1;
       bf16x8 knext0, knext1, vnext0, vnext1;
@@ -227,6 +305,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
         for (int sub = 0; sub < 2; ++sub) {
           const int qi0 = i0 + 16 * sub;
           if (causal && j0 >= qi0 + kQT) continue; // tile fully past diagonal
+          if constexpr (kDoc) {
+            if (j0 + kKTF <= sub_start[sub]) continue; // tile wholly in earlier documents
+          }
 
           // ---- S^T = K Q^T for four 16-key quarters ----
           float sv[16]; // h*4 + r: key = j0 + 16h + 4grp + r, query = row16
@@ -241,13 +322,20 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               float s = acc[r] * scale2; // log2-domain scores
-              if (causal) {
+              if constexpr (kDoc) {
+                // start[q] <= key <= min(q, N - 1) as one unsigned range
+                // test: the document, causal and ragged masks together
                 const int key_g = j0 + 16 * h + 4 * grp + r;
-                const int q_g = qi0 + row16;
-                if (key_g > q_g) s = -1e30f;
-              }
-              if constexpr (kRagged) {
-                if (j0 + 16 * h + 4 * grp + r >= N) s = -1e30f; // clamped duplicate key
+                if ((unsigned)(key_g - q_start[sub]) > q_span[sub]) s = -1e30f;
+              } else {
+                if (causal) {
+                  const int key_g = j0 + 16 * h + 4 * grp + r;
+                  const int q_g = qi0 + row16;
+                  if (key_g > q_g) s = -1e30f;
+                }
+                if constexpr (kRagged) {
+                  if (j0 + 16 * h + 4 * grp + r >= N) s = -1e30f; // clamped duplicate key
+                }
               }
               sv[h * 4 + r] = s;
             }
@@ -340,8 +428,23 @@ static Strides strides_of(const at::Tensor& t) {
   return Strides{t.stride(0), t.stride(1), t.stride(2)};
 }
 
+// doc_start, when given: int32 [B, N], contiguous, on q's device, causal
+// only. Returns its data pointer (nullptr when absent).
+static const int* checked_doc_start(const c10::optional<at::Tensor>& doc_start,
+                                    const at::Tensor& q, bool causal) {
+  if (!doc_start.has_value() || !doc_start->defined()) return nullptr;
+  const at::Tensor& ds = *doc_start;
+  TORCH_CHECK(causal, "doc_start requires causal attention");
+  TORCH_CHECK(ds.scalar_type() == at::kInt, "doc_start must be int32");
+  TORCH_CHECK(ds.device() == q.device(), "doc_start must be on q's device");
+  TORCH_CHECK(ds.dim() == 2 && ds.size(0) == q.size(0) && ds.size(1) == q.size(2),
+              "doc_start must be [B, N]");
+  TORCH_CHECK(ds.is_contiguous(), "doc_start must be contiguous");
+  return ds.data_ptr<int>();
+}
+
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
-              double scale, bool causal) {
+              double scale, bool causal, c10::optional<at::Tensor> doc_start) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "q must be bf16 [B,H,N,D]");
   TORCH_CHECK(q.dim() == 4 && q.size(3) == kAttnD, "v1 supports head dim 64");
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
@@ -359,13 +462,24 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
   const int blocks = (int)std::min<int64_t>(total_blocks, kMaxGrid);
   auto stream = c10::hip::getCurrentHIPStream();
   // aligned N keeps the unmasked instruction stream; anything else takes
-  // the clamped/masked/predicated instantiation
-  auto kernel = (N % kKTF == 0) ? attn_fwd_kernel<false> : attn_fwd_kernel<true>;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
-                     (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                     (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
-                     lse.data_ptr<float>(), BH, H, N, (float)scale, causal, strides_of(q),
-                     strides_of(k), strides_of(v));
+  // the clamped/masked/predicated instantiation, and a doc_start the kDoc
+  // instantiation of either
+  const int* dsp = checked_doc_start(doc_start, q, causal);
+  const bool ragged = N % kKTF != 0;
+  auto launch = [&](auto kernel, auto doc) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
+                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
+                       (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
+                       lse.data_ptr<float>(), BH, H, N, (float)scale, causal, strides_of(q),
+                       strides_of(k), doc);
+  };
+  if (dsp) {
+    launch(ragged ? attn_fwd_kernel<true, true> : attn_fwd_kernel<false, true>,
+           StridesDoc<true>{strides_of(v), dsp});
+  } else {
+    launch(ragged ? attn_fwd_kernel<true, false> : attn_fwd_kernel<false, false>,
+           StridesDoc<false>{strides_of(v)});
+  }
 }
 
 // ===========================================================================
@@ -414,13 +528,14 @@ __global__ void __launch_bounds__(kBlock) attn_bwd_delta_kernel(
 // Block = 4 waves, each owning a 16-key tile of one (b,h); q-tiles of 32
 // rows (Q and dO staged in shared LDS) stream past. Per q-tile, per wave:
 // 2 MFMAs S^T, 2 MFMAs dP^T, 4+4 MFMAs dV/dK accumulation (k = 32 q rows).
-template <bool kRagged>
+template <bool kRagged, bool kDoc>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dk, __hip_bfloat16* __restrict__ dv, int BH, int H, int N,
-    float scale, bool causal, Strides sq, Strides sk, Strides sv, Strides sdo) {
+    float scale, bool causal_arg, Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
+  const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   constexpr int kQStep = 32; // q rows per iteration (MFMA contraction width)
   __shared__ __hip_bfloat16 q_lds[kQStep * kAttnD]; // tiled (vt_idx) image
   __shared__ __hip_bfloat16 do_lds[kQStep * kAttnD]; // tiled (vt_idx) image
@@ -481,8 +596,27 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     // steps from kb0 to the one holding N - 1 cover every q in [j, N);
     // the per-wave skip only drops steps with i0 + 32 <= j0, i.e. whose
     // q rows are all below every key of the wave.
+    // Documents (kDoc): p = 0 for key < start[q], start[q] = dstart(q)
+    // loaded next to lse/delta for each 16-q half. i_start is unchanged
+    // (the diagonal step is where a key's own document begins to read
+    // it). A well-formed doc_start is non-decreasing, so once the first
+    // row of a q-step starts behind this block's last key (kb0 + 63), no
+    // row of this or any later step can reach a key of the block: leave
+    // the loop. The test depends on (bh, kb0, i0) only, so the break is
+    // block-uniform and sits before the step's barriers. A malformed
+    // doc_start can only end the loop early (fewer terms, never a fault).
+    const int* dsp = nullptr;
+    if constexpr (kDoc) dsp = sdo.doc_start + (int64_t)(bh / H) * N;
     const int i_start = causal ? (kb0 & ~(kQStep - 1)) : 0; // block-aligned diag
+    // (the start of the NEXT step's first row is loaded a step ahead, so
+    // the test does not wait on memory in front of the barrier)
+    int step_start = 0;
+    if constexpr (kDoc) step_start = dstart(dsp, i_start, N);
     for (int i0 = i_start; i0 < N; i0 += kQStep) {
+      if constexpr (kDoc) {
+        if (step_start > kb0 + keys_per_block - 1) break;
+        step_start = dstart(dsp, i0 + kQStep, N);
+      }
       // ---- stage Q and dO into tiled images (one bf16x8 per thread) ----
       const int st_t = vt_idx(st_row, st_col);
       const int st_g = crow<kRagged>(i0 + st_row, N);
@@ -498,6 +632,13 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
           const int qr = crow<kRagged>(q0 + row16, N);
           const float lse2_q = lsep[qr] * 1.44269504f; // log2 domain
           const float del_q = delp[qr];
+          // kDoc: row q reads keys q_lo <= key <= q_hi = q (causal); a
+          // padded row q >= N gets the empty range (q_hi = -1 < q_lo)
+          int q_lo = 0, q_hi = 0;
+          if constexpr (kDoc) {
+            q_lo = dstart(dsp, q0 + row16, N);
+            q_hi = (!kRagged || q0 + row16 < N) ? q0 + row16 : -1;
+          }
 
           // ---- S^T = K Q^T (rows = key, cols = q) ----
           f32x4 acc = {0, 0, 0, 0};
@@ -518,8 +659,14 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
             const int key_g = j0 + 4 * grp + r;
             const int q_g = q0 + row16;
             float p = 0.0f;
-            if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
-              p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
+            if constexpr (kDoc) {
+              if (key_g >= q_lo && key_g <= q_hi) { // q_hi < N: covers key < N too
+                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
+              }
+            } else {
+              if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
+                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
+              }
             }
             const float ds = p * (dpt[r] - del_q) * scale;
             // [key][q] slices: q column of this half = 16*hq + row16
@@ -573,13 +720,14 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
 // ------------------------------------------------------------------- dQ
 // Mirror of the forward: block = 4 waves x one 16-q tile; 32-key KV tiles
 // (K and V staged shared). dq[q][d] += dS[q][key] @ K[key][d].
-template <bool kRagged>
+template <bool kRagged, bool kDoc>
 __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
-    __hip_bfloat16* __restrict__ dq, int BH, int H, int N, float scale, bool causal, Strides sq,
-    Strides sk, Strides sv, Strides sdo) {
+    __hip_bfloat16* __restrict__ dq, int BH, int H, int N, float scale, bool causal_arg,
+    Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
+  const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   __shared__ __hip_bfloat16 k_lds[kKT * kAttnD]; // tiled (vt_idx) image
   __shared__ __hip_bfloat16 v_lds[kKT][kKVStride];
   __shared__ __hip_bfloat16 ds_lds_all[kWavesPerBlock][kQT][kPStride]; // [q][key32]
@@ -635,14 +783,34 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
     const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
     const int my_kv_end = causal ? (i0 + kQT) : N;
 
-    for (int j0 = 0; j0 < kv_end_block; j0 += kKT) {
+    // Documents (kDoc): p = 0 for key < start[q]; a lane owns one query,
+    // so start[q] = dstart(q) is one register (q_lo). The key walk
+    // begins at the 32-key tile holding start[qb0] (j_begin: depends on
+    // (bh, qb0) only, so the barriers stay block-uniform), and a wave
+    // also passes over tiles that end at or before start[i0] (wave_start,
+    // wave-uniform; the barriers sit outside that branch). A stored row
+    // q >= i0 >= qb0 keeps its diagonal: start[qb0] <= qb0 <= q and
+    // start[i0] <= i0 <= q, so the tile holding key q is at or after
+    // both. With a well-formed (non-decreasing) doc_start the first row
+    // has the smallest start and no row loses a key.
+    int j_begin = 0, q_lo = 0, q_hi = 0, wave_start = 0;
+    if constexpr (kDoc) {
+      const int* dsp = sdo.doc_start + (int64_t)(bh / H) * N;
+      j_begin = dstart(dsp, qb0, N) & ~(kKT - 1);
+      q_lo = dstart(dsp, i0 + row16, N);
+      // causal upper end; a padded row q >= N gets the empty range
+      q_hi = (!kRagged || i0 + row16 < N) ? i0 + row16 : -1;
+      wave_start = __builtin_amdgcn_readfirstlane(dstart(dsp, i0, N));
+    }
+
+    for (int j0 = j_begin; j0 < kv_end_block; j0 += kKT) {
       const int st_g = crow<kRagged>(j0 + st_row, N);
       *(bf16x8*)(&k_lds[vt_idx(st_row, st_col)]) =
           *(const bf16x8*)(kp + (int64_t)st_g * sk.r + st_col);
       *(bf16x8*)(&v_lds[st_row][st_col]) = *(const bf16x8*)(vp + (int64_t)st_g * sv.r + st_col);
       __syncthreads();
 
-      if (valid && j0 < my_kv_end) {
+      if (valid && j0 < my_kv_end && (!kDoc || j0 + kKT > wave_start)) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) { // two 16-key halves
           // S^T rows = key (4grp+r), col = q (row16)
@@ -662,8 +830,16 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
             const int key_g = j0 + 16 * h + 4 * grp + r;
             const int q_g = i0 + row16;
             float p = 0.0f;
-            if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
-              p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q); // lse_q in log2 domain
+            if constexpr (kDoc) {
+              if (key_g >= q_lo && key_g <= q_hi) { // q_hi < N: covers key < N too
+                // lse_q in log2 domain
+                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q);
+              }
+            } else {
+              if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
+                // lse_q in log2 domain
+                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q);
+              }
             }
             dsw[r] = (__bf16)(p * (dpt[r] - del_q) * scale);
           }
@@ -706,7 +882,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
 
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Tensor o,
               at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor delta,
-              double scale, bool causal) {
+              double scale, bool causal, c10::optional<at::Tensor> doc_start) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "q must be bf16 [B,H,N,D]");
   TORCH_CHECK(q.dim() == 4 && q.size(3) == kAttnD, "bwd supports head dim 64");
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() && dout.sizes() == q.sizes() &&
@@ -734,25 +910,35 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
 
   const int64_t kv_blocks = (int64_t)BH * ((N + 63) / 64);
   const bool ragged = N % 64 != 0; // see crow(): <false> is the aligned code
-  auto dkdv_kernel = ragged ? attn_bwd_dkdv_kernel<true> : attn_bwd_dkdv_kernel<false>;
-  auto dq_kernel = ragged ? attn_bwd_dq_kernel<true> : attn_bwd_dq_kernel<false>;
-  hipLaunchKernelGGL(dkdv_kernel, dim3((int)std::min<int64_t>(kv_blocks, kMaxGrid)),
-                     dim3(kWavesPerBlock * kWave), 0, stream,
-                     (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                     (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr(), BH, H, N,
-                     (float)scale, causal, strides_of(q), strides_of(k), strides_of(v),
-                     strides_of(dout));
-
+  const int* dsp = checked_doc_start(doc_start, q, causal);
   const int64_t q_blocks = (int64_t)BH * ((N + 63) / 64);
-  hipLaunchKernelGGL(dq_kernel, dim3((int)std::min<int64_t>(q_blocks, kMaxGrid)),
-                     dim3(kWavesPerBlock * kWave), 0, stream,
-                     (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                     (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     (__hip_bfloat16*)dq.data_ptr(), BH, H, N, (float)scale, causal,
-                     strides_of(q), strides_of(k), strides_of(v), strides_of(dout));
+  auto launch = [&](auto dkdv_kernel, auto dq_kernel, auto doc) {
+    hipLaunchKernelGGL(dkdv_kernel, dim3((int)std::min<int64_t>(kv_blocks, kMaxGrid)),
+                       dim3(kWavesPerBlock * kWave), 0, stream,
+                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
+                       (const __hip_bfloat16*)v.data_ptr(),
+                       (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(), (__hip_bfloat16*)dk.data_ptr(),
+                       (__hip_bfloat16*)dv.data_ptr(), BH, H, N, (float)scale, causal,
+                       strides_of(q), strides_of(k), strides_of(v), doc);
+    hipLaunchKernelGGL(dq_kernel, dim3((int)std::min<int64_t>(q_blocks, kMaxGrid)),
+                       dim3(kWavesPerBlock * kWave), 0, stream,
+                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
+                       (const __hip_bfloat16*)v.data_ptr(),
+                       (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(), (__hip_bfloat16*)dq.data_ptr(), BH, H, N,
+                       (float)scale, causal, strides_of(q), strides_of(k), strides_of(v),
+                       doc);
+  };
+  if (dsp) {
+    launch(ragged ? attn_bwd_dkdv_kernel<true, true> : attn_bwd_dkdv_kernel<false, true>,
+           ragged ? attn_bwd_dq_kernel<true, true> : attn_bwd_dq_kernel<false, true>,
+           StridesDoc<true>{strides_of(dout), dsp});
+  } else {
+    launch(ragged ? attn_bwd_dkdv_kernel<true, false> : attn_bwd_dkdv_kernel<false, false>,
+           ragged ? attn_bwd_dq_kernel<true, false> : attn_bwd_dq_kernel<false, false>,
+           StridesDoc<false>{strides_of(dout)});
+  }
 }
 
 } // namespace dmlamd

@@ -6,8 +6,16 @@ sync, hipGraph-captured steps inside a TrainValStage.
 
 Run:  python examples/gpt2.py
       torchrun --standalone --nproc-per-node 8 examples/gpt2.py
+      python examples/gpt2.py --packed    # several documents per row
+
+--packed fills every row with random-length documents that end in an EOS
+token, keeps attention inside each document (ops.fused_attn: the native
+kernels skip the tiles of other documents) and restarts the positions at
+every document start. The last token of a document has no next token of
+its own, so its target is the loss's ignore_index.
 """
 
+import argparse
 import sys
 
 sys.path.insert(0, './')
@@ -16,6 +24,7 @@ import torch
 
 from dmlcloud_amd import TrainingPipeline, TrainValStage
 from dmlcloud_amd.models import gpt2_small, gpt2_tiny
+from dmlcloud_amd.ops import document_starts_from_eos
 from dmlcloud_amd.parallel import FlatAdam, init_process_group_auto
 
 
@@ -31,7 +40,48 @@ class SyntheticTokens(torch.utils.data.Dataset):
         return self.tokens[idx]
 
 
+EOS_ID = 0
+IGNORE_INDEX = -100  # ops.fused_loss.cross_entropy's default
+
+
+class PackedSyntheticTokens(torch.utils.data.Dataset):
+    """Rows of `seq_len` tokens, each a run of random-length documents
+    (tokens 1..vocab-1) that end in EOS_ID; the last one is cut off by the
+    end of the row, as a packing data loader would."""
+
+    def __init__(self, n: int, seq_len: int, vocab: int, mean_len: int, seed: int = 0):
+        g = torch.Generator().manual_seed(seed)
+        self.tokens = torch.randint(1, vocab, (n, seq_len), generator=g)
+        for row in self.tokens:
+            end = -1
+            while True:
+                end += int(torch.randint(2, 2 * mean_len, (1,), generator=g))
+                if end >= seq_len:
+                    break
+                row[end] = EOS_ID
+
+    def __len__(self):
+        return len(self.tokens)
+
+    def __getitem__(self, idx):
+        return self.tokens[idx]
+
+
+def packed_targets(idx: torch.Tensor, doc_start: torch.Tensor) -> torch.Tensor:
+    """Next-token targets that never cross a document: position i
+    predicts token i + 1 unless i is the last token of its document (or of
+    the row), which gets IGNORE_INDEX. No host sync."""
+    targets = torch.full_like(idx, IGNORE_INDEX)
+    same_doc = doc_start[:, 1:] == doc_start[:, :-1]
+    targets[:, :-1] = torch.where(same_doc, idx[:, 1:], targets[:, :-1])
+    return targets
+
+
 class GPT2Stage(TrainValStage):
+    def __init__(self, packed: bool = False):
+        super().__init__()
+        self.packed = packed
+
     def pre_stage(self):
         on_gpu = self.device.type == 'cuda'
         model = gpt2_small() if on_gpu else gpt2_tiny()
@@ -42,8 +92,13 @@ class GPT2Stage(TrainValStage):
 
         vocab = replica.module.cfg.vocab_size
         seq = min(replica.module.cfg.n_positions, 1024)
-        train = SyntheticTokens(256, seq, vocab)
-        val = SyntheticTokens(32, seq, vocab, seed=1)
+        if self.packed:
+            mean_len = max(seq // 5, 4)
+            train = PackedSyntheticTokens(256, seq, vocab, mean_len)
+            val = PackedSyntheticTokens(32, seq, vocab, mean_len, seed=1)
+        else:
+            train = SyntheticTokens(256, seq, vocab)
+            val = SyntheticTokens(32, seq, vocab, seed=1)
         sampler = torch.utils.data.distributed.DistributedSampler(train)
         self.pipeline.register_dataset(
             'train', torch.utils.data.DataLoader(train, batch_size=8, sampler=sampler)
@@ -55,6 +110,11 @@ class GPT2Stage(TrainValStage):
 
     def step(self, batch):
         idx = batch.to(self.device)
+        if self.packed:
+            doc_ids = document_starts_from_eos(idx, EOS_ID)
+            targets = packed_targets(idx, doc_ids)
+            _, loss = self.pipeline.models['gpt2'](idx, targets=targets, doc_ids=doc_ids)
+            return loss
         _, loss = self.pipeline.models['gpt2'](idx, targets=idx)
         return loss
 
@@ -63,9 +123,13 @@ class GPT2Stage(TrainValStage):
 
 
 def main():
+    parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    parser.add_argument('--packed', action='store_true', help='pack several documents into each row')
+    args = parser.parse_args()
+
     init_process_group_auto()
     pipeline = TrainingPipeline(name='gpt2-synthetic')
-    pipeline.append_stage(GPT2Stage(), max_epochs=2)
+    pipeline.append_stage(GPT2Stage(packed=args.packed), max_epochs=2)
     pipeline.run()
 
 

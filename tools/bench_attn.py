@@ -1,5 +1,8 @@
 """Micro-benchmark: MFMA attention forward/backward vs SDPA (AOTriton),
-aligned shapes plus one ragged sequence length (N=1000)."""
+aligned shapes plus one ragged sequence length (N=1000), plus packed
+sequences (document mask) at the GPT-2 shape: the native kDoc kernels
+beside the dense native causal kernels and beside torch SDPA given the
+equivalent boolean attn_mask."""
 
 import math
 import os
@@ -78,6 +81,61 @@ def bench_bwd(b, h, n, d=64, causal=True):
     )
 
 
+def doc_layouts(n):
+    """name -> document lengths for one row of n tokens (all rows alike)."""
+    g = torch.Generator().manual_seed(1234)
+    lengths = []
+    while sum(lengths) < n:  # uniform on [1, 399]: mean 200
+        lengths.append(min(int(torch.randint(1, 400, (1,), generator=g)), n - sum(lengths)))
+    return {
+        '1 doc': [n],
+        f'{n // 128} docs of 128': [128] * (n // 128),
+        f'{len(lengths)} random docs (mean ~200)': lengths,
+    }
+
+
+def bench_doc(b, h, n, d=64):
+    """Forward and backward, causal, per layout: native with doc_start |
+    native dense causal (no mask: the cost to compare against) | torch
+    SDPA with the boolean [B, 1, N, N] mask a user builds today."""
+    from dmlcloud_amd.ops.fused_attn import document_mask, sdpa
+
+    torch.manual_seed(0)
+    mk = lambda: (torch.randn(b, h, n, d, device=DEV) * 0.5).to(torch.bfloat16).requires_grad_(True)
+    q, k, v = mk(), mk(), mk()
+    do = (torch.randn(b, h, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    o = torch.empty(b, h, n, d, dtype=torch.bfloat16, device=DEV)
+    lse = torch.empty(b, h, n, dtype=torch.float32, device=DEV)
+    scale = 1.0 / math.sqrt(d)
+
+    def bwd_timer(out):
+        def run():
+            q.grad = k.grad = v.grad = None
+            out.backward(do, retain_graph=True)
+
+        return time_fn(run, reps=20)
+
+    with torch.no_grad():
+        f_dense = time_fn(lambda: _C.attn_fwd(q, k, v, o, lse, scale, True))
+    b_dense = bwd_timer(sdpa(q, k, v, causal=True))
+
+    for name, lengths in doc_layouts(n).items():
+        starts = torch.tensor([0] + lengths[:-1]).cumsum(0)
+        row = torch.repeat_interleave(starts, torch.tensor(lengths)).to(torch.int32)
+        ds = row.unsqueeze(0).expand(b, n).contiguous().to(DEV)
+        mask = document_mask(ds, causal=True)
+        with torch.no_grad():
+            f_doc = time_fn(lambda: _C.attn_fwd(q, k, v, o, lse, scale, True, ds))
+            f_mask = time_fn(lambda: torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask))
+        b_doc = bwd_timer(sdpa(q, k, v, causal=True, doc_start=ds))
+        b_mask = bwd_timer(torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask))
+        for tag, t_doc, t_dense, t_mask in (('DOC FWD', f_doc, f_dense, f_mask), ('DOC BWD', b_doc, b_dense, b_mask)):
+            print(
+                f'{tag} B={b} H={h} N={n} {name}: doc {t_doc:8.1f}us | dense {t_dense:8.1f}us '
+                f'({t_dense / t_doc:4.2f}x) | masked sdpa {t_mask:8.1f}us ({t_mask / t_doc:4.2f}x)'
+            )
+
+
 if __name__ == '__main__':
     bench(64, 12, 1024)  # the GPT-2 bench shape
     bench(64, 12, 1024, causal=False)
@@ -90,3 +148,5 @@ if __name__ == '__main__':
     # walk exactly the tiles of the N=1024 rows above; sdpa beside each
     bench(64, 12, 1000)
     bench_bwd(64, 12, 1000)
+    # packed sequences at the GPT-2 shape (needs the doc_start bindings)
+    bench_doc(64, 12, 1024)
