@@ -142,6 +142,34 @@ def fused_adam_bf16(param, grad, master, exp_avg, exp_avg_sq, step_t, lr, beta1,
         )
 
 
+def fused_adamw_grouped(
+    param, grad, exp_avg, exp_avg_sq, step_t, group_map, hyper, sched, derived, last_lr, grad_scale=1.0, master=None
+):
+    """One grouped AdamW step (decoupled decay) on flat buffers: a prepare
+    launch (step += 1, schedule multiplier and bias corrections from the
+    DEVICE step into `derived` / `last_lr`) and one update kernel.
+
+    group_map uint8[n / 8] holds the group of each 8-element chunk; hyper
+    fp32[G, 8] = {lr, weight_decay, beta1, beta2, eps, ...} per group; sched
+    fp64[4] = {kind, warmup, total, min_ratio}. Nothing step-dependent is a
+    launch argument, so a captured step stays correct under replay.
+    master=None: fp32 param/grad; otherwise bf16 param/grad, fp32 master."""
+    if param.is_cuda:
+        _require_ext()
+        if master is None:
+            _C.fused_adamw_grouped(
+                param, grad, exp_avg, exp_avg_sq, step_t, group_map, hyper, sched, derived, last_lr, grad_scale
+            )
+        else:
+            _C.fused_adamw_grouped_bf16(
+                param, grad, master, exp_avg, exp_avg_sq, step_t, group_map, hyper, sched, derived, last_lr, grad_scale
+            )
+    else:
+        ref.fused_adamw_grouped_step(
+            param, grad, master, exp_avg, exp_avg_sq, step_t, group_map, hyper, sched, derived, last_lr, grad_scale
+        )
+
+
 def fused_sgd_bf16(param, grad, master, momentum_buf, lr, momentum, weight_decay, grad_scale=1.0):
     use_momentum = momentum_buf is not None and momentum != 0
     if param.is_cuda:

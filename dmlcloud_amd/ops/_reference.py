@@ -173,6 +173,77 @@ def fused_sgd_step(
     param.add_(g, alpha=-lr)
 
 
+# Schedule kinds of the grouped AdamW (keep in sync with csrc/optim.hip)
+SCHED_CONSTANT = 0
+SCHED_WARMUP_COSINE = 1
+SCHED_WARMUP_LINEAR = 2
+
+
+def adamw_schedule_multiplier(step: torch.Tensor, sched: torch.Tensor) -> torch.Tensor:
+    """LR multiplier of `step` (fp64 scalar tensor, 1-based) for the
+    schedule record fp64[4] {kind, warmup, total, min_ratio}. Tensor ops
+    only, so it never leaves the device `step` lives on."""
+    kind, warmup, total, min_ratio = sched.unbind()
+    progress = (step - warmup) / (total - warmup)
+    cosine = 0.5 * (1.0 + torch.cos(torch.pi * progress))
+    shape = torch.where(kind == SCHED_WARMUP_COSINE, cosine, 1.0 - progress)
+    mult = min_ratio + (1.0 - min_ratio) * shape
+    mult = torch.where(step >= total, min_ratio, mult)
+    mult = torch.where((warmup > 0) & (step <= warmup), step / warmup.clamp(min=1.0), mult)
+    return torch.where(kind == SCHED_CONSTANT, torch.ones_like(mult), mult)
+
+
+def adamw_prepare(
+    step_t: torch.Tensor, hyper: torch.Tensor, sched: torch.Tensor, derived: torch.Tensor, last_lr: torch.Tensor
+):
+    """step_t += 1, then fill derived fp32[G, 8] = {lr_t, decay_mul,
+    step_size, inv_sqrt_bc2, beta1, beta2, eps, 0} and last_lr fp32[G] from
+    hyper fp32[G, 8] = {lr, weight_decay, beta1, beta2, eps, ...}. The
+    schedule and the bias corrections are computed in fp64."""
+    step_t += 1
+    s = step_t[0].to(torch.float64)
+    h = hyper.to(torch.float64)
+    lr_t = (h[:, 0] * adamw_schedule_multiplier(s, sched)).to(torch.float32)
+    derived[:, 0] = lr_t
+    derived[:, 1] = (1.0 - lr_t.to(torch.float64) * h[:, 1]).to(torch.float32)
+    derived[:, 2] = (lr_t.to(torch.float64) / (1.0 - h[:, 2] ** s)).to(torch.float32)
+    derived[:, 3] = (1.0 / (1.0 - h[:, 3] ** s).sqrt()).to(torch.float32)
+    derived[:, 4:7] = hyper[:, 2:5]
+    derived[:, 7] = 0.0
+    last_lr.copy_(lr_t)
+
+
+def fused_adamw_grouped_step(
+    param: torch.Tensor,
+    grad: torch.Tensor,
+    master: Optional[torch.Tensor],
+    exp_avg: torch.Tensor,
+    exp_avg_sq: torch.Tensor,
+    step_t: torch.Tensor,
+    group_map: torch.Tensor,
+    hyper: torch.Tensor,
+    sched: torch.Tensor,
+    derived: torch.Tensor,
+    last_lr: torch.Tensor,
+    grad_scale: float,
+):
+    """Grouped AdamW (decoupled decay) on flat buffers, torch.optim.AdamW's
+    order. group_map is uint8[n / 8]: the group of each 8-element chunk.
+    master=None: fp32 param/grad; otherwise bf16 param/grad over the fp32
+    master, and param = bf16(master) afterwards."""
+    adamw_prepare(step_t, hyper, sched, derived, last_lr)
+    row = group_map.repeat_interleave(8).long().clamp_(max=hyper.shape[0] - 1)
+    decay_mul, step_size, inv_sqrt_bc2, beta1, beta2, eps = (derived[:, k][row] for k in range(1, 7))
+    w = param if master is None else master
+    g = grad.to(torch.float32) * grad_scale
+    w.mul_(decay_mul)
+    exp_avg.mul_(beta1).add_((1.0 - beta1) * g)
+    exp_avg_sq.mul_(beta2).add_((1.0 - beta2) * g * g)
+    w.sub_(step_size * exp_avg / (exp_avg_sq.sqrt() * inv_sqrt_bc2 + eps))
+    if master is not None:
+        param.copy_(master.to(torch.bfloat16))
+
+
 def l2_norm(flat: torch.Tensor) -> torch.Tensor:
     return flat.to(torch.float32).norm(2).reshape(1)
 

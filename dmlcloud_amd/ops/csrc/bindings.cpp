@@ -29,6 +29,14 @@ void fused_adam_bf16(at::Tensor param, at::Tensor grad, at::Tensor master, at::T
 void fused_sgd_bf16(at::Tensor param, at::Tensor grad, at::Tensor master,
                     at::Tensor momentum_buf, double lr, double momentum, double weight_decay,
                     double grad_scale, bool use_momentum);
+void fused_adamw_grouped(at::Tensor param, at::Tensor grad, at::Tensor exp_avg,
+                         at::Tensor exp_avg_sq, at::Tensor step_t, at::Tensor group_map,
+                         at::Tensor hyper, at::Tensor sched, at::Tensor derived,
+                         at::Tensor last_lr, double grad_scale);
+void fused_adamw_grouped_bf16(at::Tensor param, at::Tensor grad, at::Tensor master,
+                              at::Tensor exp_avg, at::Tensor exp_avg_sq, at::Tensor step_t,
+                              at::Tensor group_map, at::Tensor hyper, at::Tensor sched,
+                              at::Tensor derived, at::Tensor last_lr, double grad_scale);
 void l2_norm_and_scale(at::Tensor flat, at::Tensor partials, at::Tensor out, double max_norm,
                        bool apply, double norm_scale);
 
@@ -77,6 +85,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused Adam: bf16 params/grads, fp32 master + moments");
   m.def("fused_sgd_bf16", &dmlamd::fused_sgd_bf16,
         "Fused SGD: bf16 params/grads, fp32 master");
+  m.def("fused_adamw_grouped", &dmlamd::fused_adamw_grouped,
+        "Fused grouped AdamW on flat fp32 buffers, device-resident LR schedule");
+  m.def("fused_adamw_grouped_bf16", &dmlamd::fused_adamw_grouped_bf16,
+        "Fused grouped AdamW: bf16 params/grads, fp32 master + moments");
   m.def("l2_norm_and_scale", &dmlamd::l2_norm_and_scale,
         "Deterministic L2 norm + optional clip scale");
   m.def("conv3x3_relu_pool_fwd", &dmlamd::conv3x3_relu_pool_fwd,

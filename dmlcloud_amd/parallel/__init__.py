@@ -27,5 +27,13 @@ from .distributed import (  # noqa: F401
     world_size,
 )
 from .ddp import XGMI_BUCKET_CAP_MB, wrap_ddp  # noqa: F401
-from .flat import FlatAdam, FlatOptimizer, FlatReplica, FlatSGD  # noqa: F401
+from .flat import (  # noqa: F401
+    FlatAdam,
+    FlatAdamW,
+    FlatOptimizer,
+    FlatReplica,
+    FlatSGD,
+    LRSchedule,
+    weight_decay_groups,
+)
 from .graphs import GraphedStep  # noqa: F401

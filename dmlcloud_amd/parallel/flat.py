@@ -22,6 +22,7 @@ This replaces the reference's DDP construction for the hot benchmarks
 still offers torch-DDP semantics for arbitrary models.
 """
 
+import math
 from contextlib import contextmanager
 from typing import List, Optional
 
@@ -239,16 +240,30 @@ class FlatOptimizer(torch.optim.Optimizer):
 
     A real ``torch.optim.Optimizer`` subclass: ``param_groups[0]`` holds
     the live hyperparameters (the fused kernel reads ``lr`` from it each
-    step), so torch LR schedulers work unmodified —
-    ``register_optimizer('opt', FlatAdam(replica), scheduler)`` schedules
-    exactly like the stock-optimizer path. The per-param ``self.state``
-    dict stays empty; optimizer state lives in the flat moment buffers.
+    step), so torch LR schedulers work unmodified when the step runs
+    eagerly — ``register_optimizer('opt', FlatAdam(replica), scheduler)``
+    schedules exactly like the stock-optimizer path. The per-param
+    ``self.state`` dict stays empty; optimizer state lives in the flat
+    moment buffers.
+
+    Caveat under hipGraph replay (``GraphedStep``): ``FlatAdam`` and
+    ``FlatSGD`` pass ``lr`` and the other hyperparameters to their kernels
+    as launch arguments, so a captured step keeps the values of the
+    capture step for good and a scheduler's later changes to
+    ``param_groups`` have no effect, without an error. ``FlatAdamW`` keeps
+    them in device memory instead: its ``schedule`` follows the device
+    step counter inside the graph, and host-side changes reach a captured
+    step through ``sync_hyperparameters()`` between replays.
     """
 
-    def __init__(self, replica: FlatReplica, defaults: dict):
+    # one flat buffer = one param group, unless the subclass's kernel can
+    # tell groups apart (FlatAdamW)
+    _multi_group = False
+
+    def __init__(self, replica: FlatReplica, defaults: dict, params=None):
         self.replica = replica
-        super().__init__(replica.params, defaults)
-        if len(self.param_groups) != 1:
+        super().__init__(replica.params if params is None else params, defaults)
+        if not self._multi_group and len(self.param_groups) != 1:
             raise ValueError('FlatOptimizer drives ONE flat buffer = one param group')
 
     @property
@@ -409,3 +424,265 @@ class FlatSGD(FlatOptimizer):
             self.momentum_buf.copy_(state['momentum_buf'].to(self.momentum_buf.device))
         if state.get('master') is not None and self.replica.flat_master is not None:
             self.replica.flat_master.copy_(state['master'].to(self.replica.flat_master.device))
+
+
+class LRSchedule:
+    """Learning-rate multiplier as a function of the optimizer step, small
+    enough to live on the device: ``FlatAdamW`` evaluates it from its
+    device step counter, so a captured step follows it under replay with no
+    host involvement. ``multiplier()`` is the host mirror of that
+    computation.
+
+    For step ``s`` (1-based: the first ``step()`` is 1), warmup ``W``,
+    total ``T`` and minimum ratio ``r`` the multiplier is ``s / W`` for
+    ``s <= W`` (when ``W > 0``), ``r`` for ``s >= T``, and in between
+    ``r + (1 - r) * 0.5 * (1 + cos(pi * (s - W) / (T - W)))`` (cosine) or
+    the straight line from 1 to ``r`` (linear).
+    """
+
+    KINDS = ('constant', 'warmup_cosine', 'warmup_linear')  # index = device kind code
+
+    def __init__(self, kind: str = 'constant', warmup: int = 0, total: int = 0, min_ratio: float = 0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f'unknown schedule kind {kind!r}; expected one of {self.KINDS}')
+        warmup, total, min_ratio = int(warmup), int(total), float(min_ratio)
+        if kind != 'constant':
+            if warmup < 0 or total <= warmup:
+                raise ValueError('LRSchedule needs 0 <= warmup < total')
+            if not 0.0 <= min_ratio <= 1.0:
+                raise ValueError('LRSchedule needs 0 <= min_ratio <= 1')
+        self.kind = kind
+        self.warmup = warmup
+        self.total = total
+        self.min_ratio = min_ratio
+
+    @classmethod
+    def constant(cls) -> 'LRSchedule':
+        return cls('constant')
+
+    @classmethod
+    def warmup_cosine(cls, warmup: int, total: int, min_ratio: float = 0.0) -> 'LRSchedule':
+        return cls('warmup_cosine', warmup, total, min_ratio)
+
+    @classmethod
+    def warmup_linear(cls, warmup: int, total: int, min_ratio: float = 0.0) -> 'LRSchedule':
+        return cls('warmup_linear', warmup, total, min_ratio)
+
+    def multiplier(self, step: int) -> float:
+        if self.kind == 'constant':
+            return 1.0
+        s, w, t, r = float(step), float(self.warmup), float(self.total), self.min_ratio
+        if w > 0 and s <= w:
+            return s / w
+        if s >= t:
+            return r
+        progress = (s - w) / (t - w)
+        shape = 0.5 * (1.0 + math.cos(math.pi * progress)) if self.kind == 'warmup_cosine' else 1.0 - progress
+        return r + (1.0 - r) * shape
+
+    def record(self) -> List[float]:
+        """The fp64[4] device record {kind, warmup, total, min_ratio}."""
+        return [float(self.KINDS.index(self.kind)), float(self.warmup), float(self.total), self.min_ratio]
+
+    def state_dict(self) -> dict:
+        return {'kind': self.kind, 'warmup': self.warmup, 'total': self.total, 'min_ratio': self.min_ratio}
+
+    @classmethod
+    def from_state_dict(cls, state: dict) -> 'LRSchedule':
+        return cls(state['kind'], state['warmup'], state['total'], state['min_ratio'])
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.state_dict() == other.state_dict()
+
+    def __repr__(self):
+        if self.kind == 'constant':
+            return 'LRSchedule.constant()'
+        return f'LRSchedule.{self.kind}({self.warmup}, {self.total}, min_ratio={self.min_ratio})'
+
+
+def weight_decay_groups(module: torch.nn.Module, weight_decay: float, no_decay=None) -> List[dict]:
+    """The usual two parameter groups for ``FlatAdamW``: ``[decayed,
+    undecayed]``. By default parameters with ``dim() >= 2`` (matrices,
+    embedding tables) decay and the rest (biases, norm gains) do not, as
+    GPT-2 recipes do. ``no_decay(name, param) -> bool`` replaces that rule.
+    Tied weights appear once; frozen parameters are left out, as in
+    ``FlatReplica``."""
+    decay, rest = [], []
+    for name, p in module.named_parameters():  # removes duplicates (tied weights)
+        if not p.requires_grad:
+            continue
+        skip = no_decay(name, p) if no_decay is not None else p.dim() < 2
+        (rest if skip else decay).append(p)
+    return [{'params': decay, 'weight_decay': weight_decay}, {'params': rest, 'weight_decay': 0.0}]
+
+
+class FlatAdamW(FlatOptimizer):
+    """Fused AdamW on the flat buffer: decoupled weight decay, parameter
+    groups and a device-resident learning rate.
+
+    ``params=None`` puts every parameter of the replica in one group;
+    otherwise it is a torch-style list of group dicts (at most 16) that
+    together hold every replica parameter exactly once, each with optional
+    overrides of ``lr``, ``betas``, ``eps`` and ``weight_decay``
+    (``weight_decay_groups`` builds the usual decay / no-decay split). One
+    kernel still updates the whole buffer: a byte per 8-element chunk tells
+    it the chunk's group.
+
+    Hyperparameters: ``param_groups[g]`` is the live host copy, so torch LR
+    schedulers and user code change it as usual. The kernels read a device
+    table instead; ``sync_hyperparameters()`` uploads the host values, and
+    an eager ``step()`` calls it by itself whenever they changed. While a
+    hipGraph is being captured ``step()`` uploads nothing, and a replay
+    runs no host code at all: under ``GraphedStep``, call
+    ``sync_hyperparameters()`` between replays after changing a group.
+
+    ``schedule`` (an ``LRSchedule``, one per optimizer) multiplies every
+    group's ``lr``. It is evaluated on the device from the device step
+    counter, so a captured step follows warmup and decay under replay with
+    no host involvement. ``last_lr`` is a device fp32[G] tensor with the
+    rate each group used in the latest step; reading it needs no sync, and
+    it can go straight into ``track_reduce``.
+    """
+
+    _multi_group = True
+    MAX_GROUPS = 16
+
+    def __init__(
+        self,
+        replica: FlatReplica,
+        params=None,
+        lr=1e-3,
+        betas=(0.9, 0.999),
+        eps=1e-8,
+        weight_decay=1e-2,
+        schedule: Optional[LRSchedule] = None,
+    ):
+        if params is not None:
+            params = self._check_groups(replica, params)
+        super().__init__(replica, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), params)
+        self.schedule = schedule if schedule is not None else LRSchedule.constant()
+
+        n = replica.flat_param.numel()
+        dev = replica.flat_param.device
+        ngroups = len(self.param_groups)
+        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.last_lr = torch.zeros(ngroups, dtype=torch.float32, device=dev)
+        self._hyper = torch.zeros(ngroups, 8, dtype=torch.float32, device=dev)
+        self._derived = torch.zeros(ngroups, 8, dtype=torch.float32, device=dev)
+        self._sched = torch.tensor(self.schedule.record(), dtype=torch.float64, device=dev)
+        self.group_map = self._build_group_map().to(dev)
+        self._uploaded = None
+        self.sync_hyperparameters()
+
+    @classmethod
+    def _check_groups(cls, replica: FlatReplica, params) -> List[dict]:
+        params = list(params)
+        if not params or not all(isinstance(g, dict) and 'params' in g for g in params):
+            raise ValueError("FlatAdamW: params must be a list of group dicts with a 'params' entry")
+        groups = [dict(g) for g in params]
+        if len(groups) > cls.MAX_GROUPS:
+            raise ValueError(f'FlatAdamW supports at most {cls.MAX_GROUPS} parameter groups, got {len(groups)}')
+        own = {id(p) for p in replica.params}
+        seen = set()
+        for g in groups:
+            g['params'] = list(g['params'])
+            for p in g['params']:
+                if id(p) not in own:
+                    raise ValueError('FlatAdamW: a group holds a parameter that is not in the replica')
+                if id(p) in seen:
+                    raise ValueError('FlatAdamW: a parameter appears in more than one group')
+                seen.add(id(p))
+        if len(seen) != len(own):
+            raise ValueError(f'FlatAdamW: {len(own) - len(seen)} replica parameter(s) are in no group')
+        return groups
+
+    def _build_group_map(self) -> torch.Tensor:
+        """uint8[n / 8]: the group of each 8-element chunk. _flatten_params
+        aligns every parameter to 8 elements, so no chunk holds two."""
+        replica = self.replica
+        offset = {id(p): o for p, o in zip(replica.params, replica._offsets)}
+        group_map = torch.zeros(replica.flat_param.numel() // 8, dtype=torch.uint8)
+        for g, group in enumerate(self.param_groups):
+            for p in group['params']:
+                o = offset[id(p)]
+                group_map[o // 8 : (o + p.numel() + 7) // 8] = g
+        assert group_map.numel() == 0 or int(group_map.max()) < len(self.param_groups)
+        return group_map
+
+    def _host_hyperparameters(self) -> List[List[float]]:
+        rows = []
+        for group in self.param_groups:
+            beta1, beta2 = group['betas']
+            rows.append(
+                [float(group['lr']), float(group['weight_decay']), float(beta1), float(beta2), float(group['eps'])]
+                + [0.0, 0.0, 0.0]
+            )
+        return rows
+
+    def sync_hyperparameters(self):
+        """Copy the host hyperparameters (``param_groups``) into the device
+        table the kernels read. Not capturable; under ``GraphedStep`` call
+        it between replays."""
+        rows = self._host_hyperparameters()
+        for row in rows:
+            if not (0.0 <= row[2] < 1.0 and 0.0 <= row[3] < 1.0):
+                raise ValueError(f'FlatAdamW: betas must lie in [0, 1), got {(row[2], row[3])}')
+        self._hyper.copy_(torch.tensor(rows, dtype=torch.float32))
+        self._uploaded = rows
+
+    def _capturing(self) -> bool:
+        return self._hyper.is_cuda and torch.cuda.is_current_stream_capturing()
+
+    def step(self, closure=None):
+        if not self._capturing() and self._host_hyperparameters() != self._uploaded:
+            self.sync_hyperparameters()
+        ops.fused_adamw_grouped(
+            self.replica.flat_param,
+            self.replica.flat_grad,
+            self.exp_avg,
+            self.exp_avg_sq,
+            self.step_t,
+            self.group_map,
+            self._hyper,
+            self._sched,
+            self._derived,
+            self.last_lr,
+            grad_scale=self.replica.grad_scale,
+            master=self.replica.flat_master,
+        )
+
+    def state_dict(self):
+        return {
+            'groups': [
+                {k: group[k] for k in ('lr', 'betas', 'eps', 'weight_decay')} for group in self.param_groups
+            ],
+            'schedule': self.schedule.state_dict(),
+            'exp_avg': self.exp_avg,
+            'exp_avg_sq': self.exp_avg_sq,
+            'step': self.step_t,
+            'last_lr': self.last_lr,
+            'master': self.replica.flat_master,
+        }
+
+    def load_state_dict(self, state):
+        if len(state['groups']) != len(self.param_groups):
+            raise ValueError(
+                f"FlatAdamW: state has {len(state['groups'])} groups, optimizer has {len(self.param_groups)}"
+            )
+        for group, saved in zip(self.param_groups, state['groups']):
+            group['lr'] = saved['lr']
+            group['betas'] = tuple(saved['betas'])
+            group['eps'] = saved['eps']
+            group['weight_decay'] = saved['weight_decay']
+        self.schedule = LRSchedule.from_state_dict(state['schedule'])
+        self._sched.copy_(torch.tensor(self.schedule.record(), dtype=torch.float64))
+        self.exp_avg.copy_(state['exp_avg'].to(self.exp_avg.device))
+        self.exp_avg_sq.copy_(state['exp_avg_sq'].to(self.exp_avg_sq.device))
+        self.step_t.copy_(state['step'].to(self.step_t.device))
+        if state.get('last_lr') is not None:
+            self.last_lr.copy_(state['last_lr'].to(self.last_lr.device))
+        if state.get('master') is not None and self.replica.flat_master is not None:
+            self.replica.flat_master.copy_(state['master'].to(self.replica.flat_master.device))
+        self.sync_hyperparameters()

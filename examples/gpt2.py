@@ -25,7 +25,7 @@ import torch
 from dmlcloud_amd import TrainingPipeline, TrainValStage
 from dmlcloud_amd.models import gpt2_small, gpt2_tiny
 from dmlcloud_amd.ops import document_starts_from_eos
-from dmlcloud_amd.parallel import FlatAdam, init_process_group_auto
+from dmlcloud_amd.parallel import FlatAdamW, LRSchedule, init_process_group_auto, weight_decay_groups
 
 
 class SyntheticTokens(torch.utils.data.Dataset):
@@ -40,6 +40,7 @@ class SyntheticTokens(torch.utils.data.Dataset):
         return self.tokens[idx]
 
 
+MAX_EPOCHS = 2
 EOS_ID = 0
 IGNORE_INDEX = -100  # ops.fused_loss.cross_entropy's default
 
@@ -88,8 +89,6 @@ class GPT2Stage(TrainValStage):
         dtype = torch.bfloat16 if on_gpu else torch.float32
         self.pipeline.register_model('gpt2', model, ddp_impl='flat', flat_dtype=dtype)
         replica = self.pipeline.models['gpt2']
-        self.pipeline.register_optimizer('adam', FlatAdam(replica, lr=3e-4, weight_decay=0.1))
-
         vocab = replica.module.cfg.vocab_size
         seq = min(replica.module.cfg.n_positions, 1024)
         if self.packed:
@@ -107,6 +106,17 @@ class GPT2Stage(TrainValStage):
         self.pipeline.register_dataset(
             'val', torch.utils.data.DataLoader(val, batch_size=8, sampler=val_sampler)
         )
+
+        # AdamW as GPT-2 is trained: matrices and embeddings decay, norm
+        # gains and biases do not; linear warmup, then cosine decay to 10%.
+        # The schedule runs on the device from the optimizer's own step
+        # counter, so it also holds inside hipGraph-captured steps.
+        total_steps = MAX_EPOCHS * len(self.pipeline.datasets['train'])
+        schedule = LRSchedule.warmup_cosine(max(total_steps // 10, 1), total_steps, min_ratio=0.1)
+        optimizer = FlatAdamW(
+            replica, weight_decay_groups(model, 0.1), lr=3e-4, betas=(0.9, 0.95), schedule=schedule
+        )
+        self.pipeline.register_optimizer('adamw', optimizer)
 
     def step(self, batch):
         idx = batch.to(self.device)
@@ -129,7 +139,7 @@ def main():
 
     init_process_group_auto()
     pipeline = TrainingPipeline(name='gpt2-synthetic')
-    pipeline.append_stage(GPT2Stage(packed=args.packed), max_epochs=2)
+    pipeline.append_stage(GPT2Stage(packed=args.packed), max_epochs=MAX_EPOCHS)
     pipeline.run()
 
 

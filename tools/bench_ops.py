@@ -62,6 +62,60 @@ def bench_adam():
         print(f'  n={n:>10}: {us:8.1f} us  ({gbs:7.1f} GB/s of 7x traffic)')
 
 
+GPT2_FLAT = 124_439_808  # elements of gpt2_small's flat buffer
+
+
+def _adam_state(n, bf16):
+    p = torch.randn(n, device=DEV)
+    g = torch.randn(n, device=DEV)
+    if bf16:
+        return dict(param=p.to(torch.bfloat16), grad=g.to(torch.bfloat16), master=p)
+    return dict(param=p, grad=g)
+
+
+def bench_adamw(sizes=(1 << 16, 1 << 22, 1 << 26), rounds=1, reps=50):
+    """fused_adamw_grouped(_bf16) next to fused_adam(_bf16), alternating in
+    one session. Both move 28 B per element (grad read, param written,
+    master/moments read and written; the fp32 kernels read and write param
+    instead of a master); the grouped kernels add 1/8 B of group map."""
+    print('== fused_adamw_grouped vs fused_adam: us, TB/s of 28 (+1/8) B per element ==')
+    for n in sizes:
+        for bf16 in (False, True):
+            name = 'bf16' if bf16 else 'fp32'
+            s = _adam_state(n, bf16)
+            m = torch.zeros(n, device=DEV)
+            v = torch.zeros(n, device=DEV)
+            st = torch.zeros(1, dtype=torch.int32, device=DEV)
+            # two groups laid out as weight_decay_groups does: decayed first
+            group_map = (torch.arange(n // 8, device=DEV) >= int(n // 8 * 0.7)).to(torch.uint8)
+            hyper = torch.tensor(
+                [[1e-3, 0.1, 0.9, 0.999, 1e-8, 0, 0, 0], [1e-3, 0.0, 0.9, 0.999, 1e-8, 0, 0, 0]], device=DEV
+            )
+            sched = torch.tensor([1.0, 100.0, 1e6, 0.1], dtype=torch.float64, device=DEV)  # warmup_cosine
+            derived = torch.zeros(2, 8, device=DEV)
+            last_lr = torch.zeros(2, device=DEV)
+
+            def base():
+                if bf16:
+                    ops.fused_adam_bf16(s['param'], s['grad'], s['master'], m, v, st, 1e-3, 0.9, 0.999, 1e-8, 0.0)
+                else:
+                    ops.fused_adam(s['param'], s['grad'], m, v, st, 1e-3, 0.9, 0.999, 1e-8, 0.0)
+
+            def grouped():
+                ops.fused_adamw_grouped(
+                    s['param'], s['grad'], m, v, st, group_map, hyper, sched, derived, last_lr, master=s.get('master')
+                )
+
+            for r in range(rounds):
+                for label, fn, nbytes in (
+                    ('fused_adam' + ('_bf16' if bf16 else ''), base, 28.0),
+                    ('fused_adamw_grouped' + ('_bf16' if bf16 else ''), grouped, 28.125),
+                ):
+                    us = time_fn(fn, reps=reps)
+                    tbs = n * nbytes / (us / 1e6) / 1e12
+                    print(f'  n={n:>10} {name} round {r + 1} {label:>26}: {us:8.1f} us  {tbs:6.3f} TB/s')
+
+
 def bench_clip():
     print('== clip_grad_norm_ (norm + scale) ==')
     for n in [1 << 22, 1 << 26]:
@@ -72,7 +126,13 @@ def bench_clip():
 
 
 if __name__ == '__main__':
+    if '--adamw-gpt2' in sys.argv[1:]:
+        # the optimizer comparison alone, at the GPT-2 flat size: three
+        # alternating rounds, ~0.2 s of kernel time per figure
+        bench_adamw(sizes=(GPT2_FLAT,), rounds=3, reps=300)
+        sys.exit(0)
     bench_copy()
     bench_reduce()
     bench_adam()
+    bench_adamw()
     bench_clip()
