@@ -43,10 +43,10 @@ void l2_norm_and_scale(at::Tensor flat, at::Tensor partials, at::Tensor out, dou
 // smallcnn.hip
 void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor out,
                            at::Tensor argmax);
-void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tensor pooled,
-                                at::Tensor w, at::Tensor din);
-void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Tensor pooled,
-                                  at::Tensor in, at::Tensor dw, at::Tensor db);
+void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tensor w,
+                                at::Tensor din);
+void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Tensor in,
+                                  at::Tensor dw, at::Tensor db);
 
 // layernorm.hip
 void layernorm_fwd(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor y,

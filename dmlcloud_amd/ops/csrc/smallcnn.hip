@@ -12,25 +12,38 @@
 //   v2  LDS-staged per-sample workgroups           -> bwd_weight-dominated.
 //   v3  halo-padded planes (branch-free taps), bank-skewed strides,
 //       chunked bwd_weight: fwd 1439us / bwd_data 1199us / bwd_w 914us.
-//   v4  instruction-count pass:
-//       - fwd computes a 2x2 POOLED block per thread from a 6x6 window
-//         read as ds_read_b128+b64 rows (12 LDS instructions per channel
-//         instead of 64 b32), 4x fewer address computations;
-//       - bwd_data computes a 2x4 din block per thread from a 4x6 dconv
-//         window (vectorized rows, 16 reads per 8 outputs vs 144);
-//       - bwd_weight drops the scattered dconv plane entirely: the pool
-//         gradient is pre-gated into a dense per-cell (g, argmax) pair at
-//         stage time, inner loop reads 2 LDS values per cell + 9 taps.
-//       Padded geometry guarantees every vector read is 16B-aligned
-//       (guide §17) and channel strides are bank-skewed (mod 64 != 0).
-//   v4+ (this file) bwd_weight ends in one row of partials per workgroup
-//       and an ordered second-stage sum instead of one atomicAdd per tap
-//       per workgroup: run-to-run reproducible gradients; full model step
-//       at batch 16384 1.84 ms -> 1.53-1.61 ms
+//   v4  instruction-count pass: fwd computes a 2x2 POOLED block per thread
+//       from a 6x6 window read as ds_read_b128+b64 rows; bwd_data a 2x4 din
+//       block from a 4x6 dconv window; bwd_weight reads a dense per-cell
+//       (g, offset) pair + 9 taps. Padded geometry keeps every vector read
+//       16B-aligned and channel strides bank-skewed (mod 64 != 0).
+//   v4+ bwd_weight ends in one row of partials per workgroup and an ordered
+//       second-stage sum: run-to-run reproducible gradients
 //       (profiles/smallcnn_bwdw_ordered_partials.md).
+//   v5  (this file) data-movement pass, arithmetic untouched
+//       (profiles/smallcnn_pipelined.md):
+//       - the ReLU gate travels in bit 2 of the argmax byte, so neither
+//         backward kernel reads `pooled`;
+//       - staging is sample-invariant: every thread works out ONCE which
+//         16-byte pieces of a sample it owns and where they land in LDS,
+//         so the per-sample loop has no division and loads float4 /
+//         packed argmax words (scalar loads when a base is unaligned);
+//       - loads of a sample are issued together, up to four float4 per
+//         thread in flight, before any of them is written to LDS. Issuing
+//         them one sample ahead, before the math, was built and measured:
+//         faster per kernel at the conv1 shapes, but in the full step
+//         faster on one box and slower and erratic on another, so the
+//         sample loop stays fill -> barrier -> math -> barrier;
+//       - bwd_data writes all four positions of each pooled cell instead
+//         of re-zeroing its plane, and stores din as 8-byte pairs;
+//       - the reduce kernel stores dw/db instead of adding to them.
 //
 // ReLU/maxpool tie-breaking matches torch: first index wins ties, and a
 // pooled value of exactly 0 (all-negative window) propagates no gradient.
+//
+// The argmax byte is private to these kernels: bits 0-1 = position of the
+// maximum inside the 2x2 window (row-major), bit 2 = "gated" (pooled value
+// not > 0, no gradient).
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
@@ -41,6 +54,8 @@ namespace dmlamd {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
+
+constexpr int kGateBit = 4;
 
 // Padded plane geometry. Guard covers the 6x6 (fwd) / 4x6 (bwd) window
 // over-read of ragged 2x-blocks; PADW is a multiple of 4 so row starts at
@@ -66,17 +81,8 @@ __host__ __device__ __forceinline__ PlaneGeom plane_geom(int H, int W) {
   return g;
 }
 
-// Fill the interior of an (already zeroed) padded LDS region.
-__device__ __forceinline__ void fill_plane_padded(const float* __restrict__ g,
-                                                  float* __restrict__ lds, int CIN, int H,
-                                                  int W, const PlaneGeom& pg) {
-  const int plane = H * W;
-  for (int i = threadIdx.x; i < CIN * plane; i += kBlock) {
-    const int ci = i / plane;
-    const int rem = i - ci * plane;
-    const int y = rem / W, x = rem - y * W;
-    lds[ci * pg.cs + (y + 1) * pg.PADW + (x + 1)] = g[i];
-  }
+__host__ __device__ __forceinline__ int pooled_stride(int pcells) {
+  return pcells + ((pcells % 64) ? 0 : 4) + 1; // bank skew
 }
 
 __device__ __forceinline__ void stage_to_lds(const float* __restrict__ g, float* __restrict__ l,
@@ -96,31 +102,216 @@ __device__ __forceinline__ void read_row6(const float* __restrict__ p, float* __
   row[5] = b.y;
 }
 
+// ------------------------------------------------------- sample staging
+//
+// A sample's input plane is CIN*H*W contiguous floats, a multiple of 4
+// because H and W are even. It is cut into float4 pieces; thread t owns
+// pieces t, t + kBlock, ... The first PF of them are loaded into registers
+// together and then written to LDS, so their latencies overlap; pieces
+// beyond PF * kBlock, which only shapes larger than the MNIST ones have,
+// are copied one by one. Where a piece
+// lands in the padded LDS plane does not depend on the sample, so it is
+// worked out once per thread: o0 for elements 0-1, o1 for elements 2-3 (a
+// piece may straddle a row end, a pair cannot: W is even).
+
+__device__ __forceinline__ void plane_piece_offsets(int piece, int H, int W, const PlaneGeom& pg,
+                                                    int& o0, int& o1) {
+  const int e = 4 * piece, plane = H * W;
+  int ci = e / plane;
+  const int rem = e - ci * plane;
+  int y = rem / W;
+  int x = rem - y * W;
+  o0 = ci * pg.cs + (y + 1) * pg.PADW + (x + 1);
+  x += 2;
+  if (x == W) {
+    x = 0;
+    if (++y == H) {
+      y = 0;
+      ++ci;
+    }
+  }
+  o1 = ci * pg.cs + (y + 1) * pg.PADW + (x + 1);
+}
+
+__device__ __forceinline__ f4 load4(const float* __restrict__ p, bool vec) {
+  if (vec) return *(const f4*)p;
+  f4 r;
+  r.x = p[0];
+  r.y = p[1];
+  r.z = p[2];
+  r.w = p[3];
+  return r;
+}
+
+__device__ __forceinline__ void put_piece(float* __restrict__ lds, int o0, int o1, const f4 v) {
+  lds[o0] = v.x;
+  lds[o0 + 1] = v.y;
+  lds[o1] = v.z;
+  lds[o1 + 1] = v.w;
+}
+
+template <int PF>
+struct PlaneStage {
+  f4 v[PF];
+  int o0[PF], o1[PF];
+
+  __device__ __forceinline__ void init(int npieces, int H, int W, const PlaneGeom& pg) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int piece = threadIdx.x + k * kBlock;
+      o0[k] = o1[k] = 0;
+      if (piece < npieces) plane_piece_offsets(piece, H, W, pg, o0[k], o1[k]);
+    }
+  }
+  // issue the global loads of one sample's plane `g`
+  __device__ __forceinline__ void load(const float* __restrict__ g, int npieces, bool vec) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int piece = threadIdx.x + k * kBlock;
+      if (piece < npieces) v[k] = load4(g + 4 * piece, vec);
+    }
+  }
+  // write the loaded plane into the padded LDS region (halo stays zero)
+  __device__ __forceinline__ void store(const float* __restrict__ g, float* __restrict__ lds,
+                                        int npieces, bool vec, int H, int W,
+                                        const PlaneGeom& pg) const {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int piece = threadIdx.x + k * kBlock;
+      if (piece < npieces) put_piece(lds, o0[k], o1[k], v[k]);
+    }
+    for (int piece = threadIdx.x + PF * kBlock; piece < npieces; piece += kBlock) {
+      int a, b;
+      plane_piece_offsets(piece, H, W, pg, a, b);
+      put_piece(lds, a, b, load4(g + 4 * piece, vec));
+    }
+  }
+};
+
+// A sample's pooled-side tensors (dpooled fp32, argmax bytes) hold
+// `cells` = COUT*PH*PW elements, cut into groups of 4 consecutive cells;
+// thread t owns groups t, t + kBlock, ... Each cell has a sample-invariant
+// integer `code` telling the kernel where it goes in LDS (worked out once
+// per thread, -1 for the cells past the end of a ragged last group). With
+// cells % 4 == 0 and aligned bases a group is one float4 and one 32-bit
+// word of argmax bytes; otherwise it is loaded cell by cell.
+template <int PF>
+struct CellStage {
+  f4 g[PF];
+  uint32_t a[PF];
+  int code[PF][4];
+
+  template <typename CodeFn>
+  __device__ __forceinline__ void init(int cells, CodeFn code_of) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int c0 = 4 * (threadIdx.x + k * kBlock);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) code[k][j] = (c0 + j < cells) ? code_of(c0 + j) : -1;
+    }
+  }
+  static __device__ __forceinline__ void load_group(const float* __restrict__ dp,
+                                                    const uint8_t* __restrict__ am, int c0,
+                                                    int cells, bool vec, f4& gv, uint32_t& av) {
+    if (vec) {
+      gv = *(const f4*)(dp + c0);
+      av = *(const uint32_t*)(am + c0);
+    } else {
+      float t[4];
+      av = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool ok = c0 + j < cells;
+        t[j] = ok ? dp[c0 + j] : 0.0f;
+        av |= (ok ? (uint32_t)am[c0 + j] : (uint32_t)kGateBit) << (8 * j);
+      }
+      gv.x = t[0];
+      gv.y = t[1];
+      gv.z = t[2];
+      gv.w = t[3];
+    }
+  }
+  // dp / am point at the sample's first cell
+  __device__ __forceinline__ void load(const float* __restrict__ dp,
+                                       const uint8_t* __restrict__ am, int cells, bool vec) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int c0 = 4 * (threadIdx.x + k * kBlock);
+      if (c0 < cells) load_group(dp, am, c0, cells, vec, g[k], a[k]);
+    }
+  }
+  // put(code, gradient, argmax byte) places one cell in LDS
+  template <typename CodeFn, typename PutFn>
+  __device__ __forceinline__ void store(const float* __restrict__ dp,
+                                        const uint8_t* __restrict__ am, int cells, bool vec,
+                                        CodeFn code_of, PutFn put) const {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int c0 = 4 * (threadIdx.x + k * kBlock);
+      if (c0 < cells) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (code[k][j] >= 0) put(code[k][j], g[k][j], (a[k] >> (8 * j)) & 0xffu);
+        }
+      }
+    }
+    for (int c0 = 4 * (threadIdx.x + PF * kBlock); c0 < cells; c0 += 4 * kBlock) {
+      f4 gv;
+      uint32_t av;
+      load_group(dp, am, c0, cells, vec, gv, av);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (c0 + j < cells) put(code_of(c0 + j), gv[j], (av >> (8 * j)) & 0xffu);
+      }
+    }
+  }
+};
+
 // --------------------------------------------------------------- forward
 
 // Workgroup = one sample (grid-stride). Thread = (co, 2x2 pooled block).
-// LDS: [CIN][cs] halo-padded input + [COUT*CIN*9] weights.
+// LDS: [CIN][cs] halo-padded input + [COUT*CIN*9] weights + [COUT] bias.
+// Pooled values and argmax bytes are stored straight from the math loop;
+// collecting them in LDS for 16-byte stores measured 1-2% slower
+// (profiles/smallcnn_pipelined.md).
+//
+// VEC = true is the build for 16-byte-aligned bases; VEC = false decides
+// between vector and scalar loads by the run-time flag.
+template <int PF, bool VEC>
 __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_fwd_kernel(
     const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ out, uint8_t* __restrict__ argmax, int N, int CIN, int COUT, int H,
-    int W) {
+    int W, int in_vec_flag) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const bool in_vec = VEC || in_vec_flag;
   const PlaneGeom pg = plane_geom(H, W);
+  const int PH = H / 2, PW = W / 2;
+  const int ocells = COUT * PH * PW;
   float* ilds = (float*)smem; // [CIN][cs]
   float* wlds = ilds + CIN * pg.cs; // [COUT][CIN][9]
+  float* blds = wlds + COUT * CIN * 9; // [COUT]
 
   const int plane = CIN * H * W;
-  const int PH = H / 2, PW = W / 2;
+  const int npieces = plane / 4;
   const int BH = (PH + 1) / 2, BW = (PW + 1) / 2; // 2x2 pooled blocks
   const int nblocks = COUT * BH * BW;
 
+  PlaneStage<PF> st;
+  st.init(npieces, H, W, pg);
+  int n = blockIdx.x; // the launcher guarantees gridDim.x <= N
+  st.load(in + (int64_t)n * plane, npieces, in_vec);
+
   stage_to_lds(w, wlds, COUT * CIN * 9);
+  stage_to_lds(bias, blds, COUT);
   for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f; // halo, once
   __syncthreads();
+  st.store(in + (int64_t)n * plane, ilds, npieces, in_vec, H, W, pg);
+  __syncthreads();
 
-  for (int n = blockIdx.x; n < N; n += gridDim.x) {
-    fill_plane_padded(in + (int64_t)n * plane, ilds, CIN, H, W, pg);
-    __syncthreads();
+  for (; n < N; n += gridDim.x) {
+    const int nn = n + gridDim.x;
+    float* outn = out + (int64_t)n * ocells;
+    uint8_t* argn = argmax + (int64_t)n * ocells;
 
     for (int t = threadIdx.x; t < nblocks; t += kBlock) {
       const int bx = t % BW;
@@ -129,7 +320,7 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_fwd_kernel(
       const int y0 = 4 * by, x0 = 4 * bx; // padded top-left of 6x6 window
 
       float conv[4][4];
-      const float bz = bias[co];
+      const float bz = blds[co];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -176,63 +367,79 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_fwd_kernel(
           if (r1 > m) { m = r1; arg = 1; }
           if (r2 > m) { m = r2; arg = 2; }
           if (r3 > m) { m = r3; arg = 3; }
-          const int64_t oidx = (((int64_t)n * COUT + co) * PH + py) * PW + px;
-          out[oidx] = m;
-          argmax[oidx] = (uint8_t)arg;
+          if (!(m > 0.0f)) arg |= kGateBit;
+          const int cell = (co * PH + py) * PW + px;
+          outn[cell] = m;
+          argn[cell] = (uint8_t)arg;
         }
       }
     }
-    __syncthreads(); // before overwriting ilds for the next sample
+    __syncthreads(); // math done: ilds may be overwritten
+
+    if (nn < N) {
+      st.load(in + (int64_t)nn * plane, npieces, in_vec);
+      st.store(in + (int64_t)nn * plane, ilds, npieces, in_vec, H, W, pg);
+    }
+    __syncthreads(); // next plane published
   }
 }
 
 // ------------------------------------------------------------- bwd data
 
-// Scatter the relu+maxpool-folded conv gradient of one sample into a
-// halo-padded LDS plane (zeroed beforehand).
-__device__ __forceinline__ void scatter_dconv_padded(const float* __restrict__ dpooled,
-                                                     const uint8_t* __restrict__ argmax,
-                                                     const float* __restrict__ pooled,
-                                                     float* __restrict__ dclds, int64_t n,
-                                                     int COUT, int H, int W,
-                                                     const PlaneGeom& pg) {
-  const int PH = H / 2, PW = W / 2;
-  const int cells = COUT * PH * PW;
-  for (int cell = threadIdx.x; cell < cells; cell += kBlock) {
-    const int64_t pidx = n * cells + cell;
-    const float pv = pooled[pidx];
-    if (pv <= 0.0f) continue;
-    const int sub = argmax[pidx];
-    const int px = cell % PW;
-    const int py = (cell / PW) % PH;
-    const int co = cell / (PW * PH);
-    const int yy = 2 * py + (sub >> 1);
-    const int xx = 2 * px + (sub & 1);
-    dclds[co * pg.cs + (yy + 1) * pg.PADW + (xx + 1)] = dpooled[pidx];
-  }
-}
-
 // Workgroup = one sample. Thread = (ci, 2x4 din block): reads a 4x6
 // dconv window per cout (vectorized rows), 8 outputs per thread.
+// The relu+maxpool-folded conv gradient of a sample sits in a halo-padded
+// LDS plane. Every pooled cell writes all four positions of its 2x2 window
+// (the gradient at the argmax position unless gated, zero elsewhere), so
+// the interior is fully rewritten per sample and only the halo is zeroed,
+// once.
+template <int PF, bool VEC>
 __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_data_kernel(
     const float* __restrict__ dpooled, const uint8_t* __restrict__ argmax,
-    const float* __restrict__ pooled, const float* __restrict__ w, float* __restrict__ din,
-    int N, int CIN, int COUT, int H, int W) {
+    const float* __restrict__ w, float* __restrict__ din, int N, int CIN, int COUT, int H,
+    int W, int cell_vec_flag, int din_vec_flag) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const bool cell_vec = VEC || cell_vec_flag, din_vec = VEC || din_vec_flag;
   const PlaneGeom pg = plane_geom(H, W);
   float* dclds = (float*)smem; // [COUT][cs]
   float* wlds = dclds + COUT * pg.cs; // [COUT][CIN][9]
 
+  const int PH = H / 2, PW = W / 2;
+  const int pcells = PH * PW;
+  const int cells = COUT * pcells;
   const int BH = H / 2, BW = (W + 3) / 4; // 2x4 output blocks
   const int nblocks = CIN * BH * BW;
 
-  stage_to_lds(w, wlds, COUT * CIN * 9);
+  // code = LDS offset of the top-left position of the cell's 2x2 window
+  auto code_of = [&](int cell) {
+    const int co = cell / pcells;
+    const int rem = cell - co * pcells;
+    const int py = rem / PW, px = rem - py * PW;
+    return co * pg.cs + (2 * py + 1) * pg.PADW + (2 * px + 1);
+  };
+  auto put = [&](int code, float g, uint32_t a) {
+    const float v = (a & kGateBit) ? 0.0f : g;
+    const uint32_t sub = a & 3u;
+    dclds[code] = (sub == 0) ? v : 0.0f;
+    dclds[code + 1] = (sub == 1) ? v : 0.0f;
+    dclds[code + pg.PADW] = (sub == 2) ? v : 0.0f;
+    dclds[code + pg.PADW + 1] = (sub == 3) ? v : 0.0f;
+  };
 
-  for (int n = blockIdx.x; n < N; n += gridDim.x) {
-    for (int i = threadIdx.x; i < COUT * pg.cs; i += kBlock) dclds[i] = 0.0f;
-    __syncthreads();
-    scatter_dconv_padded(dpooled, argmax, pooled, dclds, n, COUT, H, W, pg);
-    __syncthreads();
+  CellStage<PF> st;
+  st.init(cells, code_of);
+  int n = blockIdx.x; // the launcher guarantees gridDim.x <= N
+  st.load(dpooled + (int64_t)n * cells, argmax + (int64_t)n * cells, cells, cell_vec);
+
+  stage_to_lds(w, wlds, COUT * CIN * 9);
+  for (int i = threadIdx.x; i < COUT * pg.cs; i += kBlock) dclds[i] = 0.0f; // halo, once
+  __syncthreads();
+  st.store(dpooled + (int64_t)n * cells, argmax + (int64_t)n * cells, cells, cell_vec, code_of,
+           put);
+  __syncthreads();
+
+  for (; n < N; n += gridDim.x) {
+    const int nn = n + gridDim.x;
 
     for (int t = threadIdx.x; t < nblocks; t += kBlock) {
       const int bx = t % BW;
@@ -266,14 +473,32 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_data_kernel(
           }
         }
       }
+      // W and x0 are even, so each pair of columns is inside the row or
+      // outside it as a whole and starts at an even element
 #pragma unroll
       for (int dy = 0; dy < 2; ++dy) {
+        float* drow = din + (((int64_t)n * CIN + ci) * H + y0 + dy) * W + x0;
 #pragma unroll
-        for (int dx = 0; dx < 4; ++dx) {
-          const int x = x0 + dx;
-          if (x < W) din[(((int64_t)n * CIN + ci) * H + y0 + dy) * W + x] = acc[dy][dx];
+        for (int dx = 0; dx < 4; dx += 2) {
+          if (x0 + dx < W) {
+            if (din_vec) {
+              f2 v;
+              v.x = acc[dy][dx];
+              v.y = acc[dy][dx + 1];
+              *(f2*)(drow + dx) = v;
+            } else {
+              drow[dx] = acc[dy][dx];
+              drow[dx + 1] = acc[dy][dx + 1];
+            }
+          }
         }
       }
+    }
+    __syncthreads(); // math done: dclds may be overwritten
+    if (nn < N) {
+      st.load(dpooled + (int64_t)nn * cells, argmax + (int64_t)nn * cells, cells, cell_vec);
+      st.store(dpooled + (int64_t)nn * cells, argmax + (int64_t)nn * cells, cells, cell_vec,
+               code_of, put);
     }
     __syncthreads();
   }
@@ -282,27 +507,34 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_data_kernel(
 // ----------------------------------------------------------- bwd weight
 
 // Workgroup = chunk of `samples` samples looped through LDS. The pool
-// gradient is pre-gated at stage time into dense per-cell (g, sub) pairs
+// gradient is pre-gated at stage time into dense per-cell (g, offset) pairs
 // (g = 0 encodes "no gradient"). Thread owns ((co,ci), slice): 9 register
 // partials across the chunk(s); LDS tree across slices; the workgroup
 // then writes ONE row of partials {dw[pairs*9], db[COUT]} to `part`
 // (row = blockIdx.x). bwd_weight_reduce_kernel sums the rows in a fixed
 // order: no atomics, so the gradient does not depend on the order in which
 // workgroups finish and is bitwise reproducible from run to run.
+//
+// The samples of a workgroup form one sequence (its chunks in ascending
+// order, each chunk's samples in ascending order), staged one after the
+// other: chunk boundaries need no special case.
+template <int PFI, int PFC, bool VEC>
 __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
     const float* __restrict__ dpooled, const uint8_t* __restrict__ argmax,
-    const float* __restrict__ pooled, const float* __restrict__ in, float* __restrict__ part,
-    int N, int CIN, int COUT, int H, int W, int samples) {
+    const float* __restrict__ in, float* __restrict__ part, int N, int CIN, int COUT, int H,
+    int W, int samples, int in_vec_flag, int cell_vec_flag) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const bool in_vec = VEC || in_vec_flag, cell_vec = VEC || cell_vec_flag;
   const PlaneGeom pg = plane_geom(H, W);
   const int iplane = CIN * H * W;
+  const int npieces = iplane / 4;
   const int PH = H / 2, PW = W / 2;
   const int pcells = PH * PW;
-  const int pstride = pcells + ((pcells % 64) ? 0 : 4) + 1; // bank skew
+  const int pstride = pooled_stride(pcells);
   float* ilds = (float*)smem; // [CIN][cs]
   float* glds = ilds + CIN * pg.cs; // [COUT][pstride] pre-gated gradients
-  float* slds = glds + COUT * pstride; // [COUT][pstride] argmax as float
-  float* redlds = slds + COUT * pstride; // [kBlock]
+  int* slds = (int*)(glds + COUT * pstride); // [COUT][pstride] offset of the argmax position
+  float* redlds = (float*)(slds + COUT * pstride); // [kBlock]
 
   const int cells = COUT * pcells;
 
@@ -317,60 +549,86 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
   float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   float accb = 0.0f;
 
-  // zero the input halo ONCE; interiors are overwritten every sample
-  for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f;
-  __syncthreads();
+  // code = (index into glds/slds) << 16 | padded-plane offset of the top-left
+  // position of the cell's window; the index is < 2^15 and the offset < 2^16
+  // (LDS holds 40960 words, glds and slds half of them at most), so a code
+  // is never negative
+  auto code_of = [&](int cell) {
+    const int cco = cell / pcells;
+    const int rem = cell - cco * pcells;
+    const int py = rem / PW, px = rem - py * PW;
+    return ((cco * pstride + rem) << 16) | (2 * py * pg.PADW + 2 * px);
+  };
+  // pre-decode the argmax into a padded-plane offset so the hot loop below
+  // needs no div/mod per cell
+  auto put = [&](int code, float g, uint32_t a) {
+    const int idx = code >> 16;
+    glds[idx] = (a & kGateBit) ? 0.0f : g;
+    slds[idx] = (code & 0xffff) + (int)((a >> 1) & 1u) * pg.PADW + (int)(a & 1u);
+  };
 
   // chunk blockIdx.x and, when the grid was capped, every gridDim.x-th
   // chunk after it; all chunks of a workgroup share its accumulators
   const int nchunks = (N + samples - 1) / samples;
-  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    const int n0 = chunk * samples;
-    const int nvalid = min(samples, N - n0);
-    for (int s = 0; s < nvalid; ++s) {
-      const int64_t n = n0 + s;
-      fill_plane_padded(in + n * iplane, ilds, CIN, H, W, pg);
-      for (int cell = threadIdx.x; cell < cells; cell += kBlock) {
-        const int64_t pidx = n * cells + cell;
-        const int cco = cell / pcells;
-        const int rem = cell - cco * pcells;
-        const float pv = pooled[pidx];
-        glds[cco * pstride + rem] = (pv > 0.0f) ? dpooled[pidx] : 0.0f;
-        // pre-decode the argmax into a padded-plane offset so the hot loop
-        // below needs no div/mod per cell (offsets < 2048 are exact floats)
-        const int sub = argmax[pidx];
-        const int px = rem % PW;
-        const int py = rem / PW;
-        const int yy = 2 * py + (sub >> 1);
-        const int xx = 2 * px + (sub & 1);
-        slds[cco * pstride + rem] = (float)(yy * pg.PADW + xx);
-      }
-      __syncthreads();
+  int chunk = blockIdx.x; // the launcher guarantees gridDim.x <= nchunks
+  int64_t n = (int64_t)chunk * samples;
+  int64_t nend = min((int64_t)N, n + samples);
 
-      if (active) {
-        const float* ip = ilds + ci * pg.cs;
-        const float* gp = glds + co * pstride;
-        const float* sp = slds + co * pstride;
-        for (int cell = slice; cell < pcells; cell += nslices) {
-          // branchless: g == 0 cells contribute 0 to every accumulator, and
-          // their stored offset still addresses in-bounds LDS — skipping
-          // them would diverge the wave at 16-lane granularity
-          const float g = gp[cell];
-          const int off = (int)sp[cell];
-          if (ci == 0) accb += g;
-          // input rows yy-1..yy+1 -> padded rows yy..yy+2, cols likewise
-          const float* iw = ip + off;
+  PlaneStage<PFI> sti;
+  CellStage<PFC> stc;
+  sti.init(npieces, H, W, pg);
+  stc.init(cells, code_of);
+  sti.load(in + n * iplane, npieces, in_vec);
+  stc.load(dpooled + n * cells, argmax + n * cells, cells, cell_vec);
+
+  // zero the input halo ONCE; interiors are overwritten every sample
+  for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f;
+  __syncthreads();
+  sti.store(in + n * iplane, ilds, npieces, in_vec, H, W, pg);
+  stc.store(dpooled + n * cells, argmax + n * cells, cells, cell_vec, code_of, put);
+  __syncthreads();
+
+  bool more = true;
+  while (more) {
+    // successor of sample n in this workgroup's sequence
+    int64_t nn = n + 1;
+    if (nn >= nend) {
+      chunk += gridDim.x;
+      nn = (int64_t)chunk * samples;
+      nend = min((int64_t)N, nn + samples);
+      more = chunk < nchunks;
+    }
+    if (active) {
+      const float* ip = ilds + ci * pg.cs;
+      const float* gp = glds + co * pstride;
+      const int* sp = slds + co * pstride;
+      for (int cell = slice; cell < pcells; cell += nslices) {
+        // branchless: g == 0 cells contribute 0 to every accumulator, and
+        // their stored offset still addresses in-bounds LDS — skipping
+        // them would diverge the wave at 16-lane granularity
+        const float g = gp[cell];
+        const int off = sp[cell];
+        if (ci == 0) accb += g;
+        // input rows yy-1..yy+1 -> padded rows yy..yy+2, cols likewise
+        const float* iw = ip + off;
 #pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
+        for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-              acc[ky * 3 + kx] = fmaf(g, iw[ky * pg.PADW + kx], acc[ky * 3 + kx]);
-            }
+          for (int kx = 0; kx < 3; ++kx) {
+            acc[ky * 3 + kx] = fmaf(g, iw[ky * pg.PADW + kx], acc[ky * 3 + kx]);
           }
         }
       }
-      __syncthreads();
     }
+    __syncthreads(); // math done: the staging regions may be overwritten
+    if (more) {
+      sti.load(in + nn * iplane, npieces, in_vec);
+      stc.load(dpooled + nn * cells, argmax + nn * cells, cells, cell_vec);
+      sti.store(in + nn * iplane, ilds, npieces, in_vec, H, W, pg);
+      stc.store(dpooled + nn * cells, argmax + nn * cells, cells, cell_vec, code_of, put);
+    }
+    __syncthreads();
+    n = nn;
   }
 
   // cross-slice reduction (skipped when nslices == 1)
@@ -404,10 +662,11 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
 }
 
 // Sums the `rows` partial rows of `part` [rows][cols] column by column in a
-// fixed order and ADDS the totals to dw (cols < ndw) / db (the rest; may be
-// null). Workgroup = kRedCols columns x kRedGroups row groups: a thread
-// sums rows g, g + kRedGroups, ... of its column, then group 0 combines
-// the kRedGroups partials through LDS in ascending order.
+// fixed order and STORES the totals to dw (cols < ndw) / db (the rest; may
+// be null), which need not be initialised. Workgroup = kRedCols columns x
+// kRedGroups row groups: a thread sums rows g, g + kRedGroups, ... of its
+// column, then group 0 combines the kRedGroups partials through LDS in
+// ascending order.
 constexpr int kRedCols = 16;
 constexpr int kRedGroups = kBlock / kRedCols;
 __global__ void __launch_bounds__(kBlock) bwd_weight_reduce_kernel(
@@ -427,9 +686,9 @@ __global__ void __launch_bounds__(kBlock) bwd_weight_reduce_kernel(
   if (g == 0 && col < cols) {
     for (int j = 1; j < kRedGroups; ++j) total += red[j][c];
     if (col < ndw) {
-      dw[col] += total;
+      dw[col] = total;
     } else if (db != nullptr) {
-      db[col - ndw] += total;
+      db[col - ndw] = total;
     }
   }
 }
@@ -437,6 +696,19 @@ __global__ void __launch_bounds__(kBlock) bwd_weight_reduce_kernel(
 // ------------------------------------------------------------ launchers
 
 static constexpr int kMaxLds = 160 * 1024;
+
+static bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p % bytes) == 0; }
+
+// dpooled as float4 and argmax as 32-bit words: every sample must start on
+// such a boundary
+static bool cells_vectorizable(const at::Tensor& dpooled, const at::Tensor& argmax, int cells) {
+  return cells % 4 == 0 && aligned_to(dpooled.data_ptr(), 16) && aligned_to(argmax.data_ptr(), 4);
+}
+
+// staging registers per thread: 1 when one float4 piece per thread covers
+// the sample (the MNIST shapes' smaller operand), else 4 (the larger one);
+// what 4 * kBlock pieces do not cover is copied piece by piece
+static int stage_depth(int pieces) { return pieces <= kBlock ? 1 : 4; }
 
 void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor out,
                            at::Tensor argmax) {
@@ -451,45 +723,65 @@ void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor
   TORCH_CHECK(b.numel() == COUT, "bias must be [COUT]");
   TORCH_CHECK(out.numel() == (int64_t)N * COUT * (H / 2) * (W / 2) && out.is_contiguous(),
               "out must be contiguous [N,COUT,H/2,W/2]");
-  TORCH_CHECK(argmax.numel() == out.numel() && argmax.scalar_type() == at::kByte,
-              "argmax must be uint8 like out");
+  TORCH_CHECK(argmax.numel() == out.numel() && argmax.scalar_type() == at::kByte &&
+                  argmax.is_contiguous(),
+              "argmax must be contiguous uint8 like out");
   const PlaneGeom pg = plane_geom(H, W);
-  const int lds_bytes = (CIN * pg.cs + COUT * CIN * 9) * (int)sizeof(float);
+  const int lds_bytes = (CIN * pg.cs + COUT * CIN * 9 + COUT) * (int)sizeof(float);
   TORCH_CHECK(lds_bytes <= kMaxLds, "plane+weights exceed LDS (", lds_bytes, " B)");
+  if (N == 0) return;
   auto stream = c10::hip::getCurrentHIPStream();
   const int blocks = std::min(N, kMaxGrid);
-  hipLaunchKernelGGL(conv3x3_relu_pool_fwd_kernel, dim3(blocks), dim3(kBlock), lds_bytes, stream,
+  const int in_vec = aligned_to(in.data_ptr(), 16);
+  const bool deep = stage_depth(CIN * H * W / 4) > 1;
+  auto kernel = in_vec ? (deep ? conv3x3_relu_pool_fwd_kernel<4, true>
+                               : conv3x3_relu_pool_fwd_kernel<1, true>)
+                       : (deep ? conv3x3_relu_pool_fwd_kernel<4, false>
+                               : conv3x3_relu_pool_fwd_kernel<1, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds_bytes, stream,
                      in.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(),
-                     out.data_ptr<float>(), argmax.data_ptr<uint8_t>(), N, CIN, COUT, H, W);
+                     out.data_ptr<float>(), argmax.data_ptr<uint8_t>(), N, CIN, COUT, H, W,
+                     in_vec);
 }
 
-void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tensor pooled,
-                                at::Tensor w, at::Tensor din) {
+void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tensor w,
+                                at::Tensor din) {
   const int N = din.size(0), CIN = din.size(1), H = din.size(2), W = din.size(3);
   const int COUT = w.size(0);
   TORCH_CHECK(w.size(1) == CIN && din.is_contiguous(), "weight/din geometry mismatch");
   TORCH_CHECK(dpooled.numel() == (int64_t)N * COUT * (H / 2) * (W / 2) &&
-                  argmax.numel() == dpooled.numel() && pooled.numel() == dpooled.numel(),
-              "dpooled/argmax/pooled must be [N,COUT,H/2,W/2]");
+                  argmax.numel() == dpooled.numel() && dpooled.is_contiguous() &&
+                  argmax.is_contiguous(),
+              "dpooled/argmax must be contiguous [N,COUT,H/2,W/2]");
   const PlaneGeom pg = plane_geom(H, W);
   const int lds_bytes = (COUT * pg.cs + COUT * CIN * 9) * (int)sizeof(float);
   TORCH_CHECK(lds_bytes <= kMaxLds, "dconv plane exceeds LDS");
+  if (N == 0) return;
   auto stream = c10::hip::getCurrentHIPStream();
   const int blocks = std::min(N, kMaxGrid);
-  hipLaunchKernelGGL(conv3x3_relu_pool_bwd_data_kernel, dim3(blocks), dim3(kBlock), lds_bytes,
-                     stream, dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(),
-                     pooled.data_ptr<float>(), w.data_ptr<float>(), din.data_ptr<float>(), N,
-                     CIN, COUT, H, W);
+  const int cells = COUT * (H / 2) * (W / 2);
+  const int cell_vec = cells_vectorizable(dpooled, argmax, cells);
+  const int din_vec = aligned_to(din.data_ptr(), 8);
+  const bool deep = stage_depth((cells + 3) / 4) > 1;
+  auto kernel = (cell_vec && din_vec) ? (deep ? conv3x3_relu_pool_bwd_data_kernel<4, true>
+                                              : conv3x3_relu_pool_bwd_data_kernel<1, true>)
+                                      : (deep ? conv3x3_relu_pool_bwd_data_kernel<4, false>
+                                              : conv3x3_relu_pool_bwd_data_kernel<1, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds_bytes, stream,
+                     dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(), w.data_ptr<float>(),
+                     din.data_ptr<float>(), N, CIN, COUT, H, W, cell_vec, din_vec);
 }
 
-void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Tensor pooled,
-                                  at::Tensor in, at::Tensor dw, at::Tensor db) {
+void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Tensor in,
+                                  at::Tensor dw, at::Tensor db) {
   const int N = in.size(0), CIN = in.size(1), H = in.size(2), W = in.size(3);
   const int COUT = dw.size(0);
   TORCH_CHECK(COUT * CIN <= kBlock, "bwd_weight supports COUT*CIN <= ", kBlock);
+  TORCH_CHECK(in.is_contiguous() && dpooled.is_contiguous() && argmax.is_contiguous(),
+              "in/dpooled/argmax must be contiguous");
   const PlaneGeom pg = plane_geom(H, W);
   const int pcells = (H / 2) * (W / 2);
-  const int pstride = pcells + ((pcells % 64) ? 0 : 4) + 1;
+  const int pstride = pooled_stride(pcells);
   const int lds_bytes =
       (CIN * pg.cs + 2 * COUT * pstride + kBlock) * (int)sizeof(float);
   TORCH_CHECK(lds_bytes <= kMaxLds, "bwd_weight staging exceeds LDS (", lds_bytes, " B)");
@@ -505,17 +797,34 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
   } else {
     while (samples < 16 && (N + samples * 2 - 1) / (samples * 2) >= 512) samples *= 2;
   }
-  if (N == 0) return;
+  if (N == 0) { // nothing to sum: the gradient of an empty batch is zero
+    dw.zero_();
+    if (db.defined()) db.zero_();
+    return;
+  }
   // one partial row per workgroup; the grid cap bounds the workspace
   const int blocks = std::min((N + samples - 1) / samples, kMaxGrid);
   const int ndw = COUT * CIN * 9;
   const int cols = ndw + COUT;
   at::Tensor part = at::empty({blocks, cols}, dw.options());
   auto stream = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(conv3x3_relu_pool_bwd_weight_kernel, dim3(blocks), dim3(kBlock), lds_bytes,
-                     stream, dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(),
-                     pooled.data_ptr<float>(), in.data_ptr<float>(), part.data_ptr<float>(), N,
-                     CIN, COUT, H, W, samples);
+  const int cells = COUT * pcells;
+  const int in_vec = aligned_to(in.data_ptr(), 16);
+  const int cell_vec = cells_vectorizable(dpooled, argmax, cells);
+  const int pfi = stage_depth(CIN * H * W / 4), pfc = stage_depth((cells + 3) / 4);
+  auto kernel =
+      (in_vec && cell_vec)
+          ? (pfi == 1 ? (pfc == 1 ? conv3x3_relu_pool_bwd_weight_kernel<1, 1, true>
+                                  : conv3x3_relu_pool_bwd_weight_kernel<1, 4, true>)
+                      : (pfc == 1 ? conv3x3_relu_pool_bwd_weight_kernel<4, 1, true>
+                                  : conv3x3_relu_pool_bwd_weight_kernel<4, 4, true>))
+          : (pfi == 1 ? (pfc == 1 ? conv3x3_relu_pool_bwd_weight_kernel<1, 1, false>
+                                  : conv3x3_relu_pool_bwd_weight_kernel<1, 4, false>)
+                      : (pfc == 1 ? conv3x3_relu_pool_bwd_weight_kernel<4, 1, false>
+                                  : conv3x3_relu_pool_bwd_weight_kernel<4, 4, false>));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds_bytes, stream,
+                     dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(), in.data_ptr<float>(),
+                     part.data_ptr<float>(), N, CIN, COUT, H, W, samples, in_vec, cell_vec);
   hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((cols + kRedCols - 1) / kRedCols),
                      dim3(kBlock), 0, stream, part.data_ptr<float>(), dw.data_ptr<float>(),
                      db.defined() ? db.data_ptr<float>() : nullptr, blocks, cols, ndw);

@@ -23,21 +23,23 @@ class _ConvReluPoolFn(torch.autograd.Function):
         pooled = torch.empty(N, COUT, H // 2, W // 2, device=x.device, dtype=x.dtype)
         argmax = torch.empty(N, COUT, H // 2, W // 2, device=x.device, dtype=torch.uint8)
         _C.conv3x3_relu_pool_fwd(x, weight, bias, pooled, argmax)
-        ctx.save_for_backward(x, weight, pooled, argmax)
+        # argmax carries the ReLU gate (bit 2), so backward needs no pooled values
+        ctx.save_for_backward(x, weight, argmax)
         ctx.need_input_grad = need_input_grad
         return pooled
 
     @staticmethod
     def backward(ctx, dpooled):
-        x, weight, pooled, argmax = ctx.saved_tensors
+        x, weight, argmax = ctx.saved_tensors
         dpooled = dpooled.contiguous()
-        dw = torch.zeros_like(weight)
-        db = torch.zeros(weight.shape[0], device=weight.device, dtype=weight.dtype)
-        _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, pooled, x, dw, db)
+        # the ordered second-stage sum stores every element of dw and db
+        dw = torch.empty_like(weight)
+        db = torch.empty(weight.shape[0], device=weight.device, dtype=weight.dtype)
+        _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db)
         dx = None
         if ctx.need_input_grad:
             dx = torch.empty_like(x)
-            _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, pooled, weight, dx)
+            _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, weight, dx)
         return dx, dw, db, None
 
 

@@ -42,12 +42,12 @@ def bench_shape(n, cin, cout, hw):
     _C.conv3x3_relu_pool_fwd(x, w, b, pooled, argmax)
     dpooled = torch.randn_like(pooled)
     din = torch.empty_like(x)
-    dw = torch.zeros_like(w)
-    db = torch.zeros_like(b)
+    dw = torch.empty_like(w)
+    db = torch.empty_like(b)
 
     t_fwd = time_fn(lambda: _C.conv3x3_relu_pool_fwd(x, w, b, pooled, argmax))
-    t_bwdd = time_fn(lambda: _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, pooled, w, din))
-    t_bwdw = time_fn(lambda: _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, pooled, x, dw, db))
+    t_bwdd = time_fn(lambda: _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, w, din))
+    t_bwdw = time_fn(lambda: _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db))
 
     # torch eager equivalents
     def torch_fwd():

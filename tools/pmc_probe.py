@@ -24,12 +24,12 @@ def main():
         argmax = torch.empty_like(pooled, dtype=torch.uint8)
         dpooled = torch.randn_like(pooled)
         din = torch.empty_like(x)
-        dw = torch.zeros_like(w)
-        db = torch.zeros_like(b)
+        dw = torch.empty_like(w)
+        db = torch.empty_like(b)
         for _ in range(3):
             _C.conv3x3_relu_pool_fwd(x, w, b, pooled, argmax)
-            _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, pooled, w, din)
-            _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, pooled, x, dw, db)
+            _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, w, din)
+            _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db)
 
     v = torch.randn(1 << 22, device=DEV)
     acc = torch.zeros(1, dtype=torch.float64, device=DEV)
