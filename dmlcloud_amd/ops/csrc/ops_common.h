@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <limits>
+#include <type_traits>
 
 namespace dmlamd {
 
@@ -17,8 +18,20 @@ constexpr int kMaxGrid = 2048; // 256 CUs x 8 blocks: grid-stride beyond this
 // Reduction op codes — keep in sync with ops/_reference.py
 enum ReduceOp : int { OP_SUM = 0, OP_MIN = 1, OP_MAX = 2 };
 
+// MIN and MAX propagate NaN for floating accumulators, like torch.minimum /
+// torch.maximum in ops/_reference.py: a NaN operand wins from either side,
+// whichever lane of a shuffle tree it sits in. Integers compare plainly.
 template <typename A, int OP>
 struct Combine;
+
+template <typename A>
+__device__ __forceinline__ bool combine_is_nan(A a) {
+  if constexpr (std::is_floating_point<A>::value) {
+    return a != a;
+  } else {
+    return false;
+  }
+}
 
 template <typename A>
 struct Combine<A, OP_SUM> {
@@ -28,7 +41,9 @@ struct Combine<A, OP_SUM> {
 
 template <typename A>
 struct Combine<A, OP_MIN> {
-  static __device__ __forceinline__ A apply(A a, A b) { return a < b ? a : b; }
+  static __device__ __forceinline__ A apply(A a, A b) {
+    return (a < b || combine_is_nan(a)) ? a : b; // b is NaN: a < b is false, b wins
+  }
   static __host__ __device__ A identity() {
     return std::numeric_limits<A>::has_infinity ? std::numeric_limits<A>::infinity()
                                                 : std::numeric_limits<A>::max();
@@ -37,7 +52,9 @@ struct Combine<A, OP_MIN> {
 
 template <typename A>
 struct Combine<A, OP_MAX> {
-  static __device__ __forceinline__ A apply(A a, A b) { return a > b ? a : b; }
+  static __device__ __forceinline__ A apply(A a, A b) {
+    return (a > b || combine_is_nan(a)) ? a : b;
+  }
   static __host__ __device__ A identity() {
     return std::numeric_limits<A>::has_infinity ? -std::numeric_limits<A>::infinity()
                                                 : std::numeric_limits<A>::lowest();

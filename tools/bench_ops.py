@@ -125,7 +125,37 @@ def bench_clip():
         print(f'  n={n:>10}: {us:8.1f} us  ({gbs:7.1f} GB/s of 3x traffic)')
 
 
+def bench_layernorm(shapes=((65536, 768),), rounds=1, reps=200):
+    """layernorm_fwd / layernorm_bwd at the GPT-2 shape (B*T = 65,536 rows
+    of 768). Forward moves 4 B per element (x read, y written), backward
+    6 B (dy and x read, dx written)."""
+    from dmlcloud_amd import _C
+
+    print('== layernorm fwd / bwd: us, TB/s of 4 / 6 B per element ==')
+    for R, D in shapes:
+        x = torch.randn(R, D, device=DEV).to(torch.bfloat16)
+        dy = torch.randn(R, D, device=DEV).to(torch.bfloat16)
+        gamma = torch.randn(D, device=DEV).to(torch.bfloat16)
+        beta = torch.randn(D, device=DEV).to(torch.bfloat16)
+        y, dx = torch.empty_like(x), torch.empty_like(x)
+        mean = torch.empty(R, dtype=torch.float32, device=DEV)
+        rstd = torch.empty(R, dtype=torch.float32, device=DEV)
+        ws = torch.empty(256 * 2 * D, dtype=torch.float32, device=DEV)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        for r in range(rounds):
+            for label, fn, nbytes in (
+                ('layernorm_fwd', lambda: _C.layernorm_fwd(x, gamma, beta, y, mean, rstd, 1e-5), 4.0),
+                ('layernorm_bwd', lambda: _C.layernorm_bwd(dy, x, mean, rstd, gamma, dx, ws, dgamma, dbeta), 6.0),
+            ):
+                us = time_fn(fn, reps=reps)
+                tbs = R * D * nbytes / (us / 1e6) / 1e12
+                print(f'  ({R}, {D}) round {r + 1} {label:>14}: {us:8.1f} us  {tbs:6.3f} TB/s')
+
+
 if __name__ == '__main__':
+    if '--layernorm-gpt2' in sys.argv[1:]:
+        bench_layernorm(rounds=3)
+        sys.exit(0)
     if '--adamw-gpt2' in sys.argv[1:]:
         # the optimizer comparison alone, at the GPT-2 flat size: three
         # alternating rounds, ~0.2 s of kernel time per figure
@@ -136,3 +166,4 @@ if __name__ == '__main__':
     bench_adam()
     bench_adamw()
     bench_clip()
+    bench_layernorm()
