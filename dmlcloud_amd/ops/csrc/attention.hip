@@ -1,25 +1,33 @@
-// EXPERIMENTAL: flash-attention forward for gfx950 (MFMA bf16, D=64).
-//
-// Correctness-first v1 of the custom attention path (docs/ROADMAP.md
-// item 1; the backward follows in round 2 — this kernel already emits
-// the per-row lse the backward needs). Tiling mirrors
-// ops/_attention_ref.py exactly; fragment maps are the empirically
-// confirmed ones (profiles/mfma_16x16x32_bf16_layout.txt):
-//
+// Flash attention for gfx950: forward and backward, MFMA bf16, head dim 64,
+// self-attention geometry, any N >= 1, optional packed documents. Tiling
+// mirrors ops/_attention_ref.py exactly. A block is 4 waves of one (b, h):
+//   attn_fwd_kernel       wave owns 32 q rows (two 16-row sub-tiles), block
+//                         128; 64-key K/V tiles stream past. Emits O, lse.
+//   attn_bwd_delta_kernel delta = rowsum(dO * O), eight lanes per row.
+//   attn_bwd_dkdv_kernel  wave owns 16 keys, block 64; 32-row Q/dO steps
+//                         stream past. Emits dK, dV.
+//   attn_bwd_dq_kernel    wave owns 16 q rows, block 64; 32-key K/V tiles
+//                         stream past. Emits dQ.
+// Fragment maps of v_mfma_f32_16x16x32_bf16, empirically confirmed
+// (profiles/mfma_16x16x32_bf16_layout.txt):
 //   A (bf16x8): lane l elem j <-> A[l%16][8*(l/16)+j]
 //   B (bf16x8): lane l elem j <-> B[8*(l/16)+j][l%16]
 //   C/D (f32x4): lane l reg r <-> D[4*(l/16)+r][l%16]
-//
-// Structure: ONE WAVE owns a 16-row Q tile and iterates 32-key KV tiles.
-// S is computed TRANSPOSED (S^T = K Q^T) so each lane's 8 scores share a
-// single query (softmax row reductions = 2 xor-shuffles); P^T goes
-// through a small per-wave LDS slice to re-enter the PV MFMA as the A
-// operand. Online softmax keeps m/sumexp in registers; the O accumulator
-// (16x64) lives in 4 C fragments.
+// S is computed TRANSPOSED (S^T = K Q^T) so each lane's scores share a
+// single query (softmax row reductions = 2 xor-shuffles); P^T / dS^T go
+// through small per-wave LDS slices to re-enter the next MFMA as the A
+// operand. B operands that need a transpose (V, dO, Q, K) are staged as
+// tiled 32x64 LDS images (vt_idx) and read back by read_tr_frag.
+// Template flags: <kRagged> (crow) and <kDoc> (dstart, StridesDoc);
+// <false, false> is the plain aligned dense code. The correctness arguments
+// (ragged tails, causal diagonal, document skips, the wipe) stand next to
+// their loops; tests/test_attention_*ref.py check the same tiles on the CPU.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_bf16.h>
+
+#include <initializer_list>
 
 #include "ops_common.h"
 
@@ -28,41 +36,74 @@ namespace dmlamd {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short short4v __attribute__((ext_vector_type(4)));
 
-constexpr int kAttnD = 64; // head dim (v1: fixed)
-constexpr int kQT = 16; // query rows per wave
+constexpr float kLog2e = 1.44269504f; // exp(x) = exp2(x * log2(e)): v_exp_f32
+constexpr float kLn2 = 0.69314718f;
+
+constexpr int kAttnD = 64; // head dim
+constexpr int kQT = 16; // query rows per MFMA tile
 constexpr int kKT = 32; // keys per kv tile (backward kernels)
 constexpr int kPStride = 40; // P_lds row stride in bf16 (16B-aligned rows, backward)
 constexpr int kWavesPerBlock = 4;
+constexpr int kAttnThreads = kWavesPerBlock * kWave;
 // K/V LDS row stride in bf16: multiple of 8 (16B-aligned vector rows) with
 // (stride/2 dwords, 64 banks) gcd = 4 so 16 simultaneous row reads at one
 // column offset span 16 distinct banks (rows at stride 88 bf16 = 44 dwords)
 constexpr int kKVStride = 88;
-// Forward v7 uses 64-key tiles: keys/softmax-round doubles, so the
-// per-round fixed costs (max/sum cross-lane reductions, running-stat
-// updates, O-accumulator rescale, P LDS round-trip waits, the block-wide
-// staging barrier) halve per key while the MFMA count per key stays
-// identical. 16 rows at stride 72 bf16 = 36 dwords hit 16 distinct banks
-// (gcd(36,64)=4).
+// Why the forward uses 64-key tiles and two q sub-tiles per wave: with 64
+// keys per softmax round the per-round fixed costs (max/sum cross-lane
+// reductions, running-stat updates, O-accumulator rescale, P LDS
+// round-trip waits, the block-wide staging barrier) halve per key while
+// the MFMA count per key stays identical, and the shared K fragments and
+// V fragment reads amortize over twice the MFMAs. 16 rows at stride 72
+// bf16 = 36 dwords hit 16 distinct banks (gcd(36,64)=4).
 constexpr int kKTF = 64; // fwd: keys per kv tile
 constexpr int kPStrideF = 72; // fwd: P_lds row stride in bf16
+
+// Block geometry, shared by the kernels and the launchers' grids.
+constexpr int kFwdRowsPerBlock = kWavesPerBlock * 2 * kQT; // 128 (2 sub-tiles per wave)
+constexpr int kBwdKeysPerBlock = kWavesPerBlock * 16; // 64 (dK/dV)
+constexpr int kDqRowsPerBlock = kWavesPerBlock * kQT; // 64
 
 // Tiled 32x64 LDS image index for ds_read_b64_tr_b16 consumption
 // (tools/tr_probe.hip): elem[(col/16*2 + row/4%2)*256 + row/8*64 +
 // row%4*16 + col%16] = T[row][col]. Row-major b128 reads also work on
 // the image (any 8 contiguous cols within a 16-col sub-tile row).
+constexpr int kImgElems = 32 * kAttnD; // one image
+constexpr int kImgSub = 4 * kWave; // elements one transposed read covers
 __device__ __forceinline__ int vt_idx(int row, int col) {
   return (((col >> 4) * 2 + ((row >> 2) & 1)) * 4 + (row >> 3)) * 64 + (row & 3) * 16 +
          (col & 15);
 }
 
-// v2: the block's 4 waves own consecutive q-tiles of ONE (b,h) and share
-// cooperatively staged K/V LDS tiles (one bf16x8 global load per thread per
-// tile — coalesced — instead of per-lane scattered loads; v1 measured
-// 97-186 TF vs AOTriton's 213-458 at the GPT-2 shape).
-// v5: each wave owns TWO 16-row q sub-tiles (32 q rows): the shared K
-// fragments and the scalar V fragment reads amortize over twice the
-// MFMAs, roughly doubling the per-tile MFMA:overhead ratio.
+// B-operand fragment T[8*(l/16) + j][16*db + l%16] of the 32x64 image at
+// `img` (empirically probed semantics, tools/tr_probe.hip: 16 contiguous
+// per-lane 8-byte addresses cover a 64-element region transposed as
+// 4x16): two hardware transpose reads, one per 4-row half.
+__device__ __forceinline__ bf16x8 read_tr_frag(const __hip_bfloat16* img, int db, int lane) {
+  bf16x8 f;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const short4v t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (__attribute__((address_space(3))) short4v*)&img[(db * 2 + half) * kImgSub + lane * 4]);
+    __builtin_memcpy((char*)&f + 8 * half, &t, 8);
+  }
+  return f;
+}
+
+// Per-thread coordinates: row16 = q (or key) index inside a 16-row tile,
+// grp = 16-lane group 0..3, (st_row, st_col) = the thread's bf16x8 piece of
+// a staged 32x64 tile.
+struct Coords {
+  int lane, wave, row16, grp, st_row, st_col;
+};
+__device__ __forceinline__ Coords thread_coords() {
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  return {lane, tid / kWave, lane & 15, lane >> 4, tid >> 3, (tid & 7) * 8};
+}
+
 // per-tensor strides (elements): batch, head, row; the last dim must be
 // contiguous. Lets the model pass transpose views without materializing.
 struct Strides {
@@ -123,12 +164,38 @@ __device__ __forceinline__ int dstart(const int* __restrict__ ds, int row, int N
   return min(max(ds[r], 0), r);
 }
 
+// Backward: the recomputed probability of the (key, q) pair with raw score
+// `s`, exp(s * scale - lse[q]) with lse2 = lse[q] * log2(e), or 0 where the
+// pair is masked. <kDoc>: row q reads keys q_lo <= key <= q_hi (the callers
+// fold the causal and ragged ends into q_hi, so q_hi < N covers key < N
+// too). Each test stands directly in its `if`, with the exp2 under it: a
+// select, or a bool computed first and tested after, makes the compiler
+// materialize the mask in registers inside the tile loops.
+template <bool kRagged, bool kDoc>
+__device__ __forceinline__ float bwd_prob(float s, float scale, float lse2, int key_g, int q_g,
+                                          int q_lo, int q_hi, bool causal, int N) {
+  float p = 0.0f;
+  if constexpr (kDoc) {
+    if (key_g >= q_lo && key_g <= q_hi) p = __builtin_amdgcn_exp2f(s * (scale * kLog2e) - lse2);
+  } else {
+    if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
+      p = __builtin_amdgcn_exp2f(s * (scale * kLog2e) - lse2);
+    }
+  }
+  return p;
+}
+
+// ---------------------------------------------------------------- forward
+// ONE WAVE owns two 16-row Q sub-tiles and iterates 64-key KV tiles that
+// the block's 4 waves (consecutive q rows of ONE (b,h)) stage together, one
+// coalesced bf16x8 global load per thread per piece. Online softmax keeps
+// m/sumexp in registers; each sub-tile's 16x64 O accumulator is 4 C frags.
 // Occupancy note: 204 VGPRs + 32 AGPRs -> 2 waves/SIMD. Forcing 3
 // waves/SIMD via amdgpu_waves_per_eu(3) spills 164 B/lane and measured
 // SLOWER (552 vs 508 us causal at the GPT-2 shape) — the spill traffic
 // in the inner loop outweighs the extra latency hiding. Keep 2 waves.
 template <bool kRagged, bool kDoc>
-__global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
+__global__ void __launch_bounds__(kAttnThreads) attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
     float* __restrict__ lse, int BH, int H, int N, float scale, bool causal_arg, Strides sq,
@@ -136,35 +203,26 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStrideF];
   __shared__ __hip_bfloat16 k_lds[2][kKTF][kKVStride];
-  // V lives in TILED images read by ds_read_b64_tr_b16 (empirically
-  // probed semantics, tools/tr_probe.hip: 16 contiguous per-lane 8-byte
-  // addresses cover a 64-element region transposed as 4x16). A 64-key
-  // tile is TWO consecutive 32x64 images (key chunk c at offset c*2048):
+  // V lives in TILED images for read_tr_frag. A 64-key tile is TWO
+  // consecutive 32x64 images (key chunk c at offset c*kImgElems):
   //   elem[c*2048 + (db*2+half)*256 + g*64 + jj*16 + cc] = V[32c+8g+4half+jj][16db+cc]
-  __shared__ __hip_bfloat16 v_tr[2][2 * kKTF * kAttnD / 2]; // [2][4096]
+  __shared__ __hip_bfloat16 v_tr[2][2 * kImgElems];
 
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int row16 = lane & 15; // q index inside the tile (and key row for K frags)
-  const int grp = lane >> 4; // 16-lane group 0..3
+  // row16: q index inside the tile (and key row for K frags). Staging: a
+  // 64x64 tile = 512 bf16x8 pieces, 2 per thread: (st_row, st_col) and
+  // (st_row + 32, st_col)
+  const auto [lane, wave, row16, grp, st_row, st_col] = thread_coords();
   __hip_bfloat16(*p_lds)[kPStrideF] = p_lds_all[wave];
-
-  // staging coords: 64x64 tile = 512 bf16x8 pieces, 2 per thread:
-  // (st_row, st_col) and (st_row + 32, st_col)
-  const int st_row = threadIdx.x >> 3;
-  const int st_col = (threadIdx.x & 7) * 8;
   // tiled V image offset for the (st_row, st_col) piece; the second
-  // piece lands at the same offset in the second 32x64 image (+2048)
-  const int st_vt = ((st_col >> 4) * 2 + ((st_row >> 2) & 1)) * 256 + (st_row >> 3) * 64 +
-                    (st_row & 3) * 16 + (st_col & 15);
+  // piece lands at the same offset in the second 32x64 image
+  const int st_vt = vt_idx(st_row, st_col);
 
-  const int qrows_per_block = kWavesPerBlock * 2 * kQT; // 128 (2 sub-tiles per wave)
-  const int nqb = (N + qrows_per_block - 1) / qrows_per_block;
+  const int nqb = (N + kFwdRowsPerBlock - 1) / kFwdRowsPerBlock;
   const int64_t total_blocks = (int64_t)BH * nqb;
 
   for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
     const int bh = blk / nqb;
-    const int qb0 = (blk - (int64_t)bh * nqb) * qrows_per_block;
+    const int qb0 = (blk - (int64_t)bh * nqb) * kFwdRowsPerBlock;
     const int i0 = qb0 + wave * 2 * kQT; // this wave's 32 q rows
     const bool valid = i0 < N;
     const __hip_bfloat16* qp = tslice(q, sq, bh, H);
@@ -184,7 +242,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
       }
     }
 
-    const float scale2 = scale * 1.44269504f; // fold log2(e): exp -> v_exp_f32
+    const float scale2 = scale * kLog2e; // fold log2(e): exp -> v_exp_f32
     float m_run[2] = {-1e30f, -1e30f};
     float s_run[2] = {0.0f, 0.0f};
     f32x4 o_acc[2][4];
@@ -203,7 +261,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
     // skipped. Rows q >= N of a partly valid wave tile compute on clamped
     // data and are never stored. Key 0 < N is in tile 0, which every
     // sub-tile visits, so m_run is finite after the first tile.
-    const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
+    const int kv_end_block = causal ? min(qb0 + kFwdRowsPerBlock, N) : N;
     const int my_kv_end = causal ? (i0 + 2 * kQT) : N;
 
     // Documents (kDoc): row q attends keys start[q] <= key <= q, with
@@ -259,7 +317,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
         *(const bf16x8*)(kp + (int64_t)crow<kRagged>(j_begin + st_row + 32, N) * sk.r + st_col);
     *(bf16x8*)(&v_tr[buf0][st_vt]) =
         *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j_begin + st_row, N) * sv.r + st_col);
-    *(bf16x8*)(&v_tr[buf0][2048 + st_vt]) =
+    *(bf16x8*)(&v_tr[buf0][kImgElems + st_vt]) =
         *(const bf16x8*)(vp + (int64_t)crow<kRagged>(j_begin + st_row + 32, N) * sv.r + st_col);
     __syncthreads();
 
@@ -281,24 +339,13 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
       }
 
       if (valid && j0 < my_kv_end) {
-        // shared V fragments for both q sub-tiles: [key chunk][D chunk],
-        // two hardware transpose reads per fragment
-        typedef short short4v __attribute__((ext_vector_type(4)));
+        // shared V fragments for both q sub-tiles: [key chunk][D chunk]
         bf16x8 vf[2][4];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
 #pragma unroll
           for (int db = 0; db < 4; ++db) {
-            const short4v t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) short4v*)&v_tr[buf][c * 2048 +
-                                                                       (db * 2 + 0) * 256 +
-                                                                       lane * 4]);
-            const short4v t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) short4v*)&v_tr[buf][c * 2048 +
-                                                                       (db * 2 + 1) * 256 +
-                                                                       lane * 4]);
-            __builtin_memcpy(&vf[c][db], &t0, 8);
-            __builtin_memcpy((char*)&vf[c][db] + 8, &t1, 8);
+            vf[c][db] = read_tr_frag(&v_tr[buf][c * kImgElems], db, lane);
           }
         }
 #pragma unroll
@@ -392,7 +439,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
         *(bf16x8*)(&k_lds[buf ^ 1][st_row][st_col]) = knext0;
         *(bf16x8*)(&k_lds[buf ^ 1][st_row + 32][st_col]) = knext1;
         *(bf16x8*)(&v_tr[buf ^ 1][st_vt]) = vnext0;
-        *(bf16x8*)(&v_tr[buf ^ 1][2048 + st_vt]) = vnext1;
+        *(bf16x8*)(&v_tr[buf ^ 1][kImgElems + st_vt]) = vnext1;
       }
       __syncthreads(); // readers of buf done AND buf^1 writes visible
     }
@@ -415,17 +462,64 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_fwd_kernel(
         }
         if (lane < 16 && (!kRagged || i0 + 16 * sub + row16 < N)) {
           // convert the log2-domain stats back to natural-log lse
-          lse[(int64_t)bh * N + i0 + 16 * sub + row16] =
-              0.69314718f * m_run[sub] + __logf(s_run[sub]);
+          lse[(int64_t)bh * N + i0 + 16 * sub + row16] = kLn2 * m_run[sub] + __logf(s_run[sub]);
         }
       }
     }
   }
 }
 
-static Strides strides_of(const at::Tensor& t) {
-  TORCH_CHECK(t.stride(3) == 1, "last dim must be contiguous");
-  return Strides{t.stride(0), t.stride(1), t.stride(2)};
+// ------------------------------------- launch plumbing (attn_fwd, attn_bwd)
+static Strides strides_of(const at::Tensor& t) { return {t.stride(0), t.stride(1), t.stride(2)}; }
+
+// The kernels' last stride argument (see StridesDoc).
+template <bool kDoc>
+static StridesDoc<kDoc> doc_strides_of(const at::Tensor& t, const int* doc_start) {
+  if constexpr (kDoc) return {strides_of(t), doc_start};
+  else return {strides_of(t)};
+}
+
+// f(bool_constant<kRagged>, bool_constant<kDoc>): an aligned N keeps the
+// unmasked code, any other the clamped/masked/predicated one; a doc_start kDoc.
+template <typename F>
+static void with_variant(bool ragged, bool has_doc, F&& f) {
+  if (ragged) {
+    has_doc ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  } else {
+    has_doc ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+  }
+}
+
+static int attn_grid(int BH, int N, int rows_per_block) {
+  const int64_t blocks = (int64_t)BH * ((N + rows_per_block - 1) / rows_per_block);
+  return (int)std::min<int64_t>(blocks, kMaxGrid);
+}
+
+// Everything both launchers require of their tensors, before any launch.
+// `strided`: bf16 on q's device, shaped like q, last dim contiguous (reached
+// through per-tensor strides). `dense`: the same, but indexed as contiguous
+// [BH, N, 64]. `row_stats` (lse, delta): fp32 on q's device, >= B*H*N elements.
+using NamedTensor = std::pair<const char*, const at::Tensor&>;
+static void check_attn_args(const at::Tensor& q, std::initializer_list<NamedTensor> strided,
+                            std::initializer_list<NamedTensor> dense,
+                            std::initializer_list<NamedTensor> row_stats) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1,
+              "q must be a device tensor [B,H,N,64] with N >= 1 (head dim 64 only)");
+  auto check = [&](const NamedTensor& a, at::ScalarType dtype, bool layout, const char* want) {
+    TORCH_CHECK(a.second.scalar_type() == dtype && a.second.device() == q.device() && layout,
+                a.first, " must be ", want, " on q's device");
+  };
+  for (const NamedTensor& a : strided) {
+    check(a, at::kBFloat16, a.second.sizes() == q.sizes() && a.second.stride(3) == 1,
+          "bf16, shaped like q (self-attention geometry), last dim contiguous,");
+  }
+  for (const NamedTensor& a : dense) {
+    check(a, at::kBFloat16, a.second.sizes() == q.sizes() && a.second.is_contiguous(),
+          "bf16, shaped like q, contiguous,");
+  }
+  for (const NamedTensor& a : row_stats) {
+    check(a, at::kFloat, a.second.numel() >= q.size(0) * q.size(1) * q.size(2), "fp32[B*H*N]");
+  }
 }
 
 // doc_start, when given: int32 [B, N], contiguous, on q's device, causal
@@ -445,41 +539,20 @@ static const int* checked_doc_start(const c10::optional<at::Tensor>& doc_start,
 
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
               double scale, bool causal, c10::optional<at::Tensor> doc_start) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "q must be bf16 [B,H,N,D]");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == kAttnD, "v1 supports head dim 64");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
-              "self-attention geometry required: k/v shapes must equal q");
-  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
-              "k/v must be bf16");
-  const int B = q.size(0), H = q.size(1), N = q.size(2);
-  TORCH_CHECK(N >= 1, "N must be at least 1");
-  TORCH_CHECK(o.is_contiguous() && o.sizes() == q.sizes(), "o must be contiguous [B,H,N,D]");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() >= (int64_t)B * H * N,
-              "lse must be fp32[B*H*N]");
-  const int BH = B * H;
-  const int qrows_per_block = kWavesPerBlock * 2 * kQT;
-  const int64_t total_blocks = (int64_t)BH * ((N + qrows_per_block - 1) / qrows_per_block);
-  const int blocks = (int)std::min<int64_t>(total_blocks, kMaxGrid);
-  auto stream = c10::hip::getCurrentHIPStream();
-  // aligned N keeps the unmasked instruction stream; anything else takes
-  // the clamped/masked/predicated instantiation, and a doc_start the kDoc
-  // instantiation of either
+  check_attn_args(q, {{"q", q}, {"k", k}, {"v", v}}, {{"o", o}}, {{"lse", lse}});
   const int* dsp = checked_doc_start(doc_start, q, causal);
-  const bool ragged = N % kKTF != 0;
-  auto launch = [&](auto kernel, auto doc) {
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), 0, stream,
+  const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
+  auto stream = c10::hip::getCurrentHIPStream();
+  static_assert(kKTF % (2 * kQT) == 0); // a wave's 32 q rows also end at N then
+  with_variant(N % kKTF != 0, dsp != nullptr, [&](auto ragged, auto doc) {
+    constexpr bool kDoc = decltype(doc)::value;
+    hipLaunchKernelGGL((attn_fwd_kernel<decltype(ragged)::value, kDoc>),
+                       dim3(attn_grid(BH, N, kFwdRowsPerBlock)), dim3(kAttnThreads), 0, stream,
                        (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
                        (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
                        lse.data_ptr<float>(), BH, H, N, (float)scale, causal, strides_of(q),
-                       strides_of(k), doc);
-  };
-  if (dsp) {
-    launch(ragged ? attn_fwd_kernel<true, true> : attn_fwd_kernel<false, true>,
-           StridesDoc<true>{strides_of(v), dsp});
-  } else {
-    launch(ragged ? attn_fwd_kernel<true, false> : attn_fwd_kernel<false, false>,
-           StridesDoc<false>{strides_of(v)});
-  }
+                       strides_of(k), doc_strides_of<kDoc>(v, dsp));
+  });
 }
 
 // ===========================================================================
@@ -529,7 +602,7 @@ __global__ void __launch_bounds__(kBlock) attn_bwd_delta_kernel(
 // rows (Q and dO staged in shared LDS) stream past. Per q-tile, per wave:
 // 2 MFMAs S^T, 2 MFMAs dP^T, 4+4 MFMAs dV/dK accumulation (k = 32 q rows).
 template <bool kRagged, bool kDoc>
-__global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
+__global__ void __launch_bounds__(kAttnThreads) attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
@@ -537,29 +610,23 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     float scale, bool causal_arg, Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   constexpr int kQStep = 32; // q rows per iteration (MFMA contraction width)
-  __shared__ __hip_bfloat16 q_lds[kQStep * kAttnD]; // tiled (vt_idx) image
-  __shared__ __hip_bfloat16 do_lds[kQStep * kAttnD]; // tiled (vt_idx) image
+  static_assert(kQStep * kAttnD == kImgElems);
+  __shared__ __hip_bfloat16 q_lds[kImgElems]; // tiled (vt_idx) image
+  __shared__ __hip_bfloat16 do_lds[kImgElems]; // tiled (vt_idx) image
   // per-wave transpose slices, [key16][q32(+skew)] rows for A-operand reads
   __shared__ __hip_bfloat16 pt_lds_all[kWavesPerBlock][16][kPStride];
   __shared__ __hip_bfloat16 dst_lds_all[kWavesPerBlock][16][kPStride];
 
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int row16 = lane & 15;
-  const int grp = lane >> 4;
+  const auto [lane, wave, row16, grp, st_row, st_col] = thread_coords(); // st_row 0..31
   __hip_bfloat16(*pt_lds)[kPStride] = pt_lds_all[wave];
   __hip_bfloat16(*dst_lds)[kPStride] = dst_lds_all[wave];
 
-  const int st_row = threadIdx.x >> 3; // 0..31
-  const int st_col = (threadIdx.x & 7) * 8;
-
-  const int keys_per_block = kWavesPerBlock * 16; // 64
-  const int nkb = (N + keys_per_block - 1) / keys_per_block;
+  const int nkb = (N + kBwdKeysPerBlock - 1) / kBwdKeysPerBlock;
   const int64_t total_blocks = (int64_t)BH * nkb;
 
   for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
     const int bh = blk / nkb;
-    const int kb0 = (blk - (int64_t)bh * nkb) * keys_per_block;
+    const int kb0 = (blk - (int64_t)bh * nkb) * kBwdKeysPerBlock;
     const int j0 = kb0 + wave * 16; // this wave's 16 keys
     const bool valid = j0 < N;
     const __hip_bfloat16* qp = tslice(q, sq, bh, H);
@@ -614,7 +681,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
     if constexpr (kDoc) step_start = dstart(dsp, i_start, N);
     for (int i0 = i_start; i0 < N; i0 += kQStep) {
       if constexpr (kDoc) {
-        if (step_start > kb0 + keys_per_block - 1) break;
+        if (step_start > kb0 + kBwdKeysPerBlock - 1) break;
         step_start = dstart(dsp, i0 + kQStep, N);
       }
       // ---- stage Q and dO into tiled images (one bf16x8 per thread) ----
@@ -630,7 +697,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
         for (int hq = 0; hq < 2; ++hq) {
           const int q0 = i0 + 16 * hq; // this half's first q row
           const int qr = crow<kRagged>(q0 + row16, N);
-          const float lse2_q = lsep[qr] * 1.44269504f; // log2 domain
+          const float lse2_q = lsep[qr] * kLog2e; // log2 domain
           const float del_q = delp[qr];
           // kDoc: row q reads keys q_lo <= key <= q_hi = q (causal); a
           // padded row q >= N gets the empty range (q_hi = -1 < q_lo)
@@ -656,18 +723,8 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
           // lane holds keys 4grp+r (rows), q = row16 (col)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int key_g = j0 + 4 * grp + r;
-            const int q_g = q0 + row16;
-            float p = 0.0f;
-            if constexpr (kDoc) {
-              if (key_g >= q_lo && key_g <= q_hi) { // q_hi < N: covers key < N too
-                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
-              }
-            } else {
-              if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
-                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse2_q);
-              }
-            }
+            const float p = bwd_prob<kRagged, kDoc>(acc[r], scale, lse2_q, j0 + 4 * grp + r,
+                                                    q0 + row16, q_lo, q_hi, causal, N);
             const float ds = p * (dpt[r] - del_q) * scale;
             // [key][q] slices: q column of this half = 16*hq + row16
             pt_lds[4 * grp + r][16 * hq + row16] = __float2bfloat16(p);
@@ -679,20 +736,10 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
         // ---- dV += P^T @ dO ; dK += dS^T @ Q  (contraction over 32 q) ----
         const bf16x8 ptf = *(const bf16x8*)(&pt_lds[row16][8 * grp]);
         const bf16x8 dstf = *(const bf16x8*)(&dst_lds[row16][8 * grp]);
-        typedef short short4v __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-          bf16x8 dob, qb;
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int base = (db * 2 + half) * 256 + lane * 4;
-            const short4v td = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) short4v*)&do_lds[base]);
-            const short4v tq = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) short4v*)&q_lds[base]);
-            __builtin_memcpy((char*)&dob + 8 * half, &td, 8);
-            __builtin_memcpy((char*)&qb + 8 * half, &tq, 8);
-          }
+          const bf16x8 dob = read_tr_frag(do_lds, db, lane);
+          const bf16x8 qb = read_tr_frag(q_lds, db, lane);
           dv_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf, dob, dv_acc[db], 0, 0, 0);
           dk_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf, qb, dk_acc[db], 0, 0, 0);
         }
@@ -721,33 +768,27 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dkdv_kernel(
 // Mirror of the forward: block = 4 waves x one 16-q tile; 32-key KV tiles
 // (K and V staged shared). dq[q][d] += dS[q][key] @ K[key][d].
 template <bool kRagged, bool kDoc>
-__global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
+__global__ void __launch_bounds__(kAttnThreads) attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dq, int BH, int H, int N, float scale, bool causal_arg,
     Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
-  __shared__ __hip_bfloat16 k_lds[kKT * kAttnD]; // tiled (vt_idx) image
+  static_assert(kKT * kAttnD == kImgElems);
+  __shared__ __hip_bfloat16 k_lds[kImgElems]; // tiled (vt_idx) image
   __shared__ __hip_bfloat16 v_lds[kKT][kKVStride];
   __shared__ __hip_bfloat16 ds_lds_all[kWavesPerBlock][kQT][kPStride]; // [q][key32]
 
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int row16 = lane & 15;
-  const int grp = lane >> 4;
+  const auto [lane, wave, row16, grp, st_row, st_col] = thread_coords();
   __hip_bfloat16(*ds_lds)[kPStride] = ds_lds_all[wave];
 
-  const int st_row = threadIdx.x >> 3;
-  const int st_col = (threadIdx.x & 7) * 8;
-
-  const int qrows_per_block = kWavesPerBlock * kQT; // 64
-  const int nqb = (N + qrows_per_block - 1) / qrows_per_block;
+  const int nqb = (N + kDqRowsPerBlock - 1) / kDqRowsPerBlock;
   const int64_t total_blocks = (int64_t)BH * nqb;
 
   for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
     const int bh = blk / nqb;
-    const int qb0 = (blk - (int64_t)bh * nqb) * qrows_per_block;
+    const int qb0 = (blk - (int64_t)bh * nqb) * kDqRowsPerBlock;
     const int i0 = qb0 + wave * kQT;
     const bool valid = i0 < N;
     const __hip_bfloat16* qp = tslice(q, sq, bh, H);
@@ -766,7 +807,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
         qf[c] = *(const bf16x8*)(qp + (int64_t)qr * sq.r + 32 * c + 8 * grp);
         dof[c] = *(const bf16x8*)(dop + (int64_t)qr * sdo.r + 32 * c + 8 * grp);
       }
-      lse_q = lsep[crow<kRagged>(i0 + row16, N)] * 1.44269504f; // log2 domain
+      lse_q = lsep[crow<kRagged>(i0 + row16, N)] * kLog2e; // log2 domain
       del_q = delp[crow<kRagged>(i0 + row16, N)];
     }
 
@@ -780,7 +821,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
     // (i0 <= q < i0 + 16) needs keys 0..q; key q sits in the tile with
     // j0 = 32 * (q / 32) <= q < min(qb0 + 64, N) = kv_end_block, and
     // j0 <= q < i0 + 16 = my_kv_end, so it is walked and not skipped.
-    const int kv_end_block = causal ? min(qb0 + qrows_per_block, N) : N;
+    const int kv_end_block = causal ? min(qb0 + kDqRowsPerBlock, N) : N;
     const int my_kv_end = causal ? (i0 + kQT) : N;
 
     // Documents (kDoc): p = 0 for key < start[q]; a lane owns one query,
@@ -827,20 +868,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
           bf16x4 dsw;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int key_g = j0 + 16 * h + 4 * grp + r;
-            const int q_g = i0 + row16;
-            float p = 0.0f;
-            if constexpr (kDoc) {
-              if (key_g >= q_lo && key_g <= q_hi) { // q_hi < N: covers key < N too
-                // lse_q in log2 domain
-                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q);
-              }
-            } else {
-              if ((!causal || key_g <= q_g) && (!kRagged || (key_g < N && q_g < N))) {
-                // lse_q in log2 domain
-                p = __builtin_amdgcn_exp2f(acc[r] * (scale * 1.44269504f) - lse_q);
-              }
-            }
+            const float p = bwd_prob<kRagged, kDoc>(acc[r], scale, lse_q,
+                                                    j0 + 16 * h + 4 * grp + r, i0 + row16, q_lo,
+                                                    q_hi, causal, N);
             dsw[r] = (__bf16)(p * (dpt[r] - del_q) * scale);
           }
           *(bf16x4*)(&ds_lds[row16][16 * h + 4 * grp]) = dsw;
@@ -848,17 +878,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
 
         // ---- dq += dS @ K (contraction over the 32 keys) ----
         const bf16x8 dsf = *(const bf16x8*)(&ds_lds[row16][8 * grp]);
-        typedef short short4v __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-          bf16x8 kb;
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const short4v tk = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) short4v*)&k_lds[(db * 2 + half) * 256 +
-                                                                   lane * 4]);
-            __builtin_memcpy((char*)&kb + 8 * half, &tk, 8);
-          }
+          const bf16x8 kb = read_tr_frag(k_lds, db, lane);
           dq_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, kb, dq_acc[db], 0, 0, 0);
         }
       }
@@ -883,23 +905,10 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) attn_bwd_dq_kernel(
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Tensor o,
               at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor delta,
               double scale, bool causal, c10::optional<at::Tensor> doc_start) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "q must be bf16 [B,H,N,D]");
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == kAttnD, "bwd supports head dim 64");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() && dout.sizes() == q.sizes() &&
-                  o.sizes() == q.sizes(),
-              "self-attention geometry required: k/v/dout/o shapes must equal q");
-  TORCH_CHECK(dout.stride(3) == 1 && o.is_contiguous(), "o contiguous; dout last-dim contig");
-  TORCH_CHECK(dq.is_contiguous() && dk.is_contiguous() && dv.is_contiguous(),
-              "grad outputs must be contiguous");
-  TORCH_CHECK(dq.sizes() == q.sizes() && dk.sizes() == q.sizes() && dv.sizes() == q.sizes(),
-              "grad output shapes must equal q");
-  const int B = q.size(0), H = q.size(1), N = q.size(2);
-  TORCH_CHECK(N >= 1, "N must be at least 1");
-  const int BH = B * H;
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() >= (int64_t)BH * N,
-              "lse must be fp32[BH*N]");
-  TORCH_CHECK(delta.numel() >= (int64_t)BH * N && delta.scalar_type() == at::kFloat,
-              "delta workspace must be fp32[BH*N]");
+  check_attn_args(q, {{"q", q}, {"k", k}, {"v", v}, {"dout", dout}},
+                  {{"o", o}, {"dq", dq}, {"dk", dk}, {"dv", dv}}, {{"lse", lse}, {"delta", delta}});
+  const int* dsp = checked_doc_start(doc_start, q, causal);
+  const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
   auto stream = c10::hip::getCurrentHIPStream();
 
   const int64_t rows = (int64_t)BH * N;
@@ -908,37 +917,23 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
                      (const __hip_bfloat16*)o.data_ptr(), delta.data_ptr<float>(), rows, H, N,
                      strides_of(dout));
 
-  const int64_t kv_blocks = (int64_t)BH * ((N + 63) / 64);
-  const bool ragged = N % 64 != 0; // see crow(): <false> is the aligned code
-  const int* dsp = checked_doc_start(doc_start, q, causal);
-  const int64_t q_blocks = (int64_t)BH * ((N + 63) / 64);
-  auto launch = [&](auto dkdv_kernel, auto dq_kernel, auto doc) {
-    hipLaunchKernelGGL(dkdv_kernel, dim3((int)std::min<int64_t>(kv_blocks, kMaxGrid)),
-                       dim3(kWavesPerBlock * kWave), 0, stream,
-                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                       (const __hip_bfloat16*)v.data_ptr(),
-                       (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), (__hip_bfloat16*)dk.data_ptr(),
-                       (__hip_bfloat16*)dv.data_ptr(), BH, H, N, (float)scale, causal,
-                       strides_of(q), strides_of(k), strides_of(v), doc);
-    hipLaunchKernelGGL(dq_kernel, dim3((int)std::min<int64_t>(q_blocks, kMaxGrid)),
-                       dim3(kWavesPerBlock * kWave), 0, stream,
-                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                       (const __hip_bfloat16*)v.data_ptr(),
-                       (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), (__hip_bfloat16*)dq.data_ptr(), BH, H, N,
-                       (float)scale, causal, strides_of(q), strides_of(k), strides_of(v),
-                       doc);
-  };
-  if (dsp) {
-    launch(ragged ? attn_bwd_dkdv_kernel<true, true> : attn_bwd_dkdv_kernel<false, true>,
-           ragged ? attn_bwd_dq_kernel<true, true> : attn_bwd_dq_kernel<false, true>,
-           StridesDoc<true>{strides_of(dout), dsp});
-  } else {
-    launch(ragged ? attn_bwd_dkdv_kernel<true, false> : attn_bwd_dkdv_kernel<false, false>,
-           ragged ? attn_bwd_dq_kernel<true, false> : attn_bwd_dq_kernel<false, false>,
-           StridesDoc<false>{strides_of(dout)});
-  }
+  // see crow(): <false> is the aligned code, for N that ends both kernels' blocks
+  const bool ragged = N % kBwdKeysPerBlock != 0 || N % kDqRowsPerBlock != 0;
+  with_variant(ragged, dsp != nullptr, [&](auto ragged_c, auto doc) {
+    constexpr bool kRagged = decltype(ragged_c)::value, kDoc = decltype(doc)::value;
+    auto launch = [&](auto kernel, int rows_per_block, auto... outputs) {
+      hipLaunchKernelGGL(kernel, dim3(attn_grid(BH, N, rows_per_block)), dim3(kAttnThreads), 0,
+                         stream, (const __hip_bfloat16*)q.data_ptr(),
+                         (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
+                         (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
+                         delta.data_ptr<float>(), outputs..., BH, H, N, (float)scale, causal,
+                         strides_of(q), strides_of(k), strides_of(v),
+                         doc_strides_of<kDoc>(dout, dsp));
+    };
+    launch(attn_bwd_dkdv_kernel<kRagged, kDoc>, kBwdKeysPerBlock, (__hip_bfloat16*)dk.data_ptr(),
+           (__hip_bfloat16*)dv.data_ptr());
+    launch(attn_bwd_dq_kernel<kRagged, kDoc>, kDqRowsPerBlock, (__hip_bfloat16*)dq.data_ptr());
+  });
 }
 
 } // namespace dmlamd

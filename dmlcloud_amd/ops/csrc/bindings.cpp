@@ -61,7 +61,7 @@ void ce_fwd(at::Tensor logits, at::Tensor targets, at::Tensor loss, at::Tensor l
 void ce_bwd(at::Tensor logits, at::Tensor targets, at::Tensor lse, at::Tensor scale,
             at::Tensor dlogits, int64_t ignore_index);
 
-// attention.hip (experimental)
+// attention.hip
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
               double scale, bool causal, c10::optional<at::Tensor> doc_start);
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Tensor o,
@@ -105,12 +105,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // doc_start is optional and trailing: the 7- and 12-argument positional
   // calls keep working
   m.def("attn_fwd", &dmlamd::attn_fwd,
-        "EXPERIMENTAL flash-attention forward (MFMA bf16, D=64, emits lse; optional "
+        "Flash-attention forward (MFMA bf16, D=64, emits lse; optional "
         "int32 doc_start[B, N] packs several documents per row)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("scale"),
         py::arg("causal"), py::arg("doc_start") = py::none());
   m.def("attn_bwd", &dmlamd::attn_bwd,
-        "EXPERIMENTAL flash-attention backward (recompute; dq/dk/dv; optional doc_start)",
+        "Flash-attention backward (recompute; dq/dk/dv; optional doc_start)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"), py::arg("o"), py::arg("lse"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("delta"), py::arg("scale"),
         py::arg("causal"), py::arg("doc_start") = py::none());

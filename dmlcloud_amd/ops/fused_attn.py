@@ -11,7 +11,8 @@ cross-attention geometry, non-bf16) falls back to torch SDPA
 takes. The fused path is ON by default whenever usable — set
 DMLCLOUD_DISABLE_FUSED_ATTN=1 to force the AOTriton path (the A/B
 ladder in profiles/ uses this switch). Numerics are verified in
-tests/test_gpu.py and tests/test_gpu_attention_ragged.py.
+tests/test_gpu.py and tests/test_gpu_attention_ragged.py (shared
+helpers: tests/attn_testlib.py).
 
 Packed sequences: `sdpa(q, k, v, causal=True, doc_start=ds)` keeps
 attention inside documents when several are packed into one batch row.
@@ -45,10 +46,7 @@ class _SdpaFn(torch.autograd.Function):
         # empty_like would inherit a transpose-view's strides; o is ours
         o = torch.empty(B, H, N, D, dtype=q.dtype, device=q.device)
         lse = torch.empty(B, H, N, dtype=torch.float32, device=q.device)
-        if doc_start is None:
-            _C.attn_fwd(q, k, v, o, lse, scale, causal)
-        else:
-            _C.attn_fwd(q, k, v, o, lse, scale, causal, doc_start)
+        _C.attn_fwd(q, k, v, o, lse, scale, causal, doc_start)
         ctx.save_for_backward(q, k, v, o, lse, doc_start)
         ctx.causal = causal
         ctx.scale = scale
@@ -64,10 +62,7 @@ class _SdpaFn(torch.autograd.Function):
         dk = torch.empty_like(dq)
         dv = torch.empty_like(dq)
         delta = torch.empty(B * H * N, dtype=torch.float32, device=q.device)
-        if doc_start is None:
-            _C.attn_bwd(q, k, v, dout, o, lse, dq, dk, dv, delta, ctx.scale, ctx.causal)
-        else:
-            _C.attn_bwd(q, k, v, dout, o, lse, dq, dk, dv, delta, ctx.scale, ctx.causal, doc_start)
+        _C.attn_bwd(q, k, v, dout, o, lse, dq, dk, dv, delta, ctx.scale, ctx.causal, doc_start)
         return dq, dk, dv, None, None, None
 
 
@@ -75,7 +70,7 @@ _INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
 
 
 def _usable(q, k, v, doc_start=None, causal=True):
-    if os.environ.get('DMLCLOUD_DISABLE_FUSED_ATTN', '0') not in ('0', '', 'false'):
+    if not fused_attention_enabled():
         return False
     # The kernels assume self-attention geometry: k/v must match q exactly
     # (cross-attention with a different kv length/head count falls back).

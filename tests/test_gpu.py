@@ -558,7 +558,7 @@ class TestFusedCE:
 
 
 class TestAttnFwdExperimental:
-    """EXPERIMENTAL flash-attention forward (attention.hip) vs SDPA and
+    """Flash attention (attention.hip), forward and backward, vs SDPA and
     the CPU tile blueprint."""
 
     @pytest.mark.parametrize('causal', [True, False])
@@ -670,6 +670,51 @@ class TestAttnFwdExperimental:
         ref_o, ref_lse = flash_attn_fwd_tiled(q[0, 0].float(), k[0, 0].float(), v[0, 0].float(), causal=True)
         torch.testing.assert_close(lse.cpu()[0, 0], ref_lse, rtol=1e-2, atol=1e-2)
         torch.testing.assert_close(o.float().cpu()[0, 0], ref_o, rtol=3e-2, atol=3e-2)
+
+
+    def test_launchers_reject_bad_tensors(self):
+        """A tensor of the wrong dtype, device or size raises in the
+        launchers' host check, before any kernel runs; the same buffers then
+        serve one valid call."""
+        import math
+
+        from attn_testlib import assert_fwd_bwd_close
+        from dmlcloud_amd import _C
+
+        torch.manual_seed(11)
+        n, d = 64, 64
+        scale = 1.0 / math.sqrt(d)
+        q, k, v, do = ((torch.randn(1, 1, n, d, device=DEV) * 0.5).to(torch.bfloat16) for _ in range(4))
+        o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
+        lse = torch.empty(1, 1, n, dtype=torch.float32, device=DEV)
+        delta = torch.empty(n, dtype=torch.float32, device=DEV)
+
+        def bwd(**bad):
+            a = dict(q=q, k=k, v=v, dout=do, o=o, lse=lse, dq=dq, dk=dk, dv=dv, delta=delta)
+            a.update(bad)
+            _C.attn_bwd(*a.values(), scale, True)
+
+        with pytest.raises(RuntimeError):
+            bwd(dout=do.float())
+        with pytest.raises(RuntimeError):
+            bwd(dq=dq.float())
+        with pytest.raises(RuntimeError):
+            bwd(dk=dk.cpu())
+        with pytest.raises(RuntimeError):
+            bwd(k=k.half())
+        with pytest.raises(RuntimeError):
+            _C.attn_fwd(q, k, v, o.float(), lse, scale, True)
+        with pytest.raises(RuntimeError):
+            _C.attn_fwd(q, k, v, o, lse.cpu(), scale, True)
+        with pytest.raises(RuntimeError):
+            bwd(delta=delta[: n - 1])
+
+        _C.attn_fwd(q, k, v, o, lse, scale, True)
+        bwd()
+        q2, k2, v2 = (t.float().requires_grad_(True) for t in (q, k, v))
+        ref = torch.nn.functional.scaled_dot_product_attention(q2, k2, v2, is_causal=True)
+        ref.backward(do.float())
+        assert_fwd_bwd_close('after rejections', (o, dq, dk, dv), (ref.detach(), q2.grad, k2.grad, v2.grad))
 
 
 class TestPipelineGPU:

@@ -16,6 +16,9 @@ import math
 import pytest
 import torch
 
+from attn_testlib import assert_fwd_bwd_close as _assert_close
+from attn_testlib import run_with_canaries
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
@@ -98,12 +101,6 @@ def _native(case):
     out = sdpa(q, k, v, causal=True, doc_start=ds)
     out.backward(do)
     return out.detach(), q.grad, k.grad, v.grad
-
-
-def _assert_close(tag, got, want):
-    for name, g, w, tol in zip(('out', 'dq', 'dk', 'dv'), got, want, (3e-2, 5e-2, 5e-2, 5e-2)):
-        print(f'{tag} {name}: max abs err {(g.float() - w.float()).abs().max().item():.3e}')
-        torch.testing.assert_close(g.float(), w.float(), rtol=tol, atol=tol)
 
 
 @pytest.mark.parametrize('case', list(CASES))
@@ -234,47 +231,8 @@ def test_tiles_of_other_documents_are_skipped_dkdv():
     torch.testing.assert_close(dv[:, :, :128].float(), rdv, rtol=5e-2, atol=5e-2)
 
 
-def _carve(numel, tail, dtype, sentinel):
-    """A tensor of `numel` NaNs at the front of a larger flat buffer whose
-    last `tail` elements hold `sentinel`."""
-    flat = torch.full((numel + tail,), sentinel, dtype=dtype, device=DEV)
-    flat[:numel] = float('nan')
-    return flat, flat[:numel]
-
-
-def _bits(t):
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
-def _run_with_canaries(n, ds):
-    """Forward and backward through the direct bindings with a sentinel
-    behind every output; returns the outputs after checking that the
-    sentinels are bit-identical and every element in front was written."""
-    from dmlcloud_amd import _C
-
-    q, k, v, do = _inputs(n)
-    bufs = {}
-    for name in ('o', 'dq', 'dk', 'dv'):
-        bufs[name] = _carve(B * H * n * D, 128 * D, torch.bfloat16, -7.5)
-    for name in ('lse', 'delta'):
-        bufs[name] = _carve(B * H * n, 128, torch.float32, -12345.0)
-    before = {name: _bits(flat).clone() for name, (flat, _) in bufs.items()}
-
-    o, dq, dk, dv = (bufs[x][1].view(B, H, n, D) for x in ('o', 'dq', 'dk', 'dv'))
-    lse = bufs['lse'][1].view(B, H, n)
-    _C.attn_fwd(q, k, v, o, lse, SCALE, True, ds)
-    _C.attn_bwd(q, k, v, do, o, lse, dq, dk, dv, bufs['delta'][1], SCALE, True, ds)
-    torch.cuda.synchronize()
-
-    for name, (flat, front) in bufs.items():
-        numel = front.numel()
-        assert torch.equal(_bits(flat)[numel:], before[name][numel:]), f'{name}: sentinel overwritten'
-        assert not torch.isnan(front).any(), f'{name}: rows left unwritten'
-    return o, lse, dq, dk, dv
-
-
 def test_canaries_untouched():
-    o, _, dq, dk, dv = _run_with_canaries(_n('RAGGED'), _doc_start('RAGGED'))
+    o, _, dq, dk, dv = run_with_canaries(_inputs(_n('RAGGED')), True, _doc_start('RAGGED'))
     _assert_close('RAGGED canaries', (o, dq, dk, dv), _reference('RAGGED'))
 
 
@@ -313,7 +271,7 @@ def test_malformed_doc_start_is_clamped(n):
     ds = torch.randint(0, 10 * n, (B, n), generator=g, dtype=torch.int32)
     ds[:, ::5] = torch.randint(0, n, (B, len(range(0, n, 5))), generator=g, dtype=torch.int32)
     ds[:, 3::11] = -9
-    for t in _run_with_canaries(n, ds.to(DEV)):
+    for t in run_with_canaries(_inputs(n), True, ds.to(DEV)):
         assert torch.isfinite(t).all()
 
 

@@ -16,6 +16,8 @@ import math
 import pytest
 import torch
 
+from attn_testlib import assert_fwd_bwd_close, run_with_canaries
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
@@ -43,15 +45,7 @@ def _reference(n, causal):
 
 
 def _check_fwd_bwd(n, causal, out, dq, dk, dv):
-    ref, rdq, rdk, rdv = _reference(n, causal)
-    for name, got, want, tol in (
-        ('out', out, ref, 3e-2),
-        ('dq', dq, rdq, 5e-2),
-        ('dk', dk, rdk, 5e-2),
-        ('dv', dv, rdv, 5e-2),
-    ):
-        print(f'N={n} causal={causal} {name}: max abs err {(got.float() - want).abs().max().item():.3e}')
-        torch.testing.assert_close(got.float(), want, rtol=tol, atol=tol)
+    assert_fwd_bwd_close(f'N={n} causal={causal}', (out, dq, dk, dv), _reference(n, causal))
 
 
 @pytest.mark.parametrize('causal', [True, False])
@@ -107,45 +101,13 @@ def test_poisoned_slack(causal, n):
     _check_fwd_bwd(n, causal, out.detach(), q.grad, k.grad, v.grad)
 
 
-def _carve(numel, tail, dtype, sentinel):
-    """A tensor of `numel` NaNs at the front of a larger flat buffer whose
-    last `tail` elements hold `sentinel`."""
-    flat = torch.full((numel + tail,), sentinel, dtype=dtype, device=DEV)
-    flat[:numel] = float('nan')
-    return flat, flat[:numel]
-
-
-def _bits(t):
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
-
-
 @pytest.mark.parametrize('causal', [True, False])
 @pytest.mark.parametrize('n', LENGTHS)
 def test_canaries_untouched(causal, n):
     """Every output is the front of a larger buffer; the 128 rows' worth
     of sentinel behind it must come back bit-identical, and every element
     in front of it must have been written (no NaN fill left)."""
-    from dmlcloud_amd import _C
-
-    q, k, v, do = _inputs(n)
-    bufs = {}
-    for name in ('o', 'dq', 'dk', 'dv'):
-        bufs[name] = _carve(B * H * n * D, 128 * D, torch.bfloat16, -7.5)
-    for name in ('lse', 'delta'):
-        bufs[name] = _carve(B * H * n, 128, torch.float32, -12345.0)
-    before = {name: _bits(flat).clone() for name, (flat, _) in bufs.items()}
-
-    o, dq, dk, dv = (bufs[x][1].view(B, H, n, D) for x in ('o', 'dq', 'dk', 'dv'))
-    lse = bufs['lse'][1].view(B, H, n)
-    delta = bufs['delta'][1]
-    _C.attn_fwd(q, k, v, o, lse, SCALE, causal)
-    _C.attn_bwd(q, k, v, do, o, lse, dq, dk, dv, delta, SCALE, causal)
-    torch.cuda.synchronize()
-
-    for name, (flat, front) in bufs.items():
-        numel = front.numel()
-        assert torch.equal(_bits(flat)[numel:], before[name][numel:]), f'{name}: sentinel overwritten'
-        assert not torch.isnan(front).any(), f'{name}: rows left unwritten'
+    run_with_canaries(_inputs(n), causal)
 
 
 def test_exact_counting():
