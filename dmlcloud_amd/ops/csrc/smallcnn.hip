@@ -20,7 +20,10 @@
 //   v4+ bwd_weight ends in one row of partials per workgroup and an ordered
 //       second-stage sum: run-to-run reproducible gradients
 //       (profiles/smallcnn_bwdw_ordered_partials.md).
-//   v5  (this file) data-movement pass, arithmetic untouched
+//   v6  (this file) conv2-like layers run fwd and bwd_data as f32 MFMA
+//       implicit GEMMs, bit for bit the VALU kernels' results
+//       (profiles/smallcnn_mfma.md); see "f32 MFMA forms" below.
+//   v5  data-movement pass, arithmetic untouched
 //       (profiles/smallcnn_pipelined.md):
 //       - the ReLU gate travels in bit 2 of the argmax byte, so neither
 //         backward kernel reads `pooled`;
@@ -504,6 +507,299 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_data_kernel(
   }
 }
 
+// ------------------------------------------- f32 MFMA forms (16 channels)
+//
+// conv2-like layers (COUT == 16, CIN in {4, 8, 12, 16}) run forward and
+// bwd_data as an implicit GEMM per sample on v_mfma_f32_16x16x4_f32. The
+// instruction is a k-ordered f32 fmaf chain, so with k in the order of the
+// loops above the results are bit for bit those of the VALU kernels; it
+// issues at the VALU's peak rate from one VGPR per operand and pads a 14x14
+// plane to 13 tiles of 16 rows (6 %) where the 4x4 blocks pad it to 16x16
+// (31 %). Staging, the padded planes and the sample loop are those of the
+// VALU kernels.
+//
+// Lane l supplies A[row l&15][k = 4s + (l>>4)] and B[k = 4s + (l>>4)][l&15]
+// at step s, and holds D[rows 4*(l>>4) .. +3][column l&15]. A row's operand
+// is one LDS word at (row's top-left offset, from a per-workgroup table) +
+// (k's offset inside the 3x3xC stencil). k = c*9 + tap, so step s+9 is step
+// s four channels on: nine per-lane k-offsets and a uniform stride suffice.
+// B is stored as [k][16], which makes a step's operand word 64*s + lane.
+//
+// Wave v owns tiles v, v+4, ... and runs up to three of them as interleaved
+// accumulator chains sharing B (a dependent MFMA has 40 cycles of latency
+// against 32 of issue). At 13 tiles that is 3+1 tiles for wave 0 and 3 for
+// the others. Measured at the conv2 shape (profiles/smallcnn_mfma.md):
+// three chains beat one, two and four; rotating the wave that carries the
+// odd tile with the sample index, and loading the next sample ahead of the
+// math, gained nothing.
+
+constexpr int kMfmaChains = 3;
+
+template <int NC>
+__device__ __forceinline__ void mfma_chains(const float* __restrict__ alds,
+                                            const float* __restrict__ wbl,
+                                            const int (&base)[kMfmaChains], const int (&koff)[9],
+                                            int groups, int gstride, f4 (&acc)[kMfmaChains]) {
+  for (int cg = 0; cg < groups; ++cg) {
+    const float* ap = alds + cg * gstride;
+    const float* bp = wbl + cg * 9 * kWave;
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+      const float b = bp[s * kWave];
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[base[i] + koff[s]], b, acc[i], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// acc[i] += A(tile of base[i]) x B for the first nc (wave-uniform) chains
+__device__ __forceinline__ void mfma_tiles(int nc, const float* __restrict__ alds,
+                                           const float* __restrict__ wbl,
+                                           const int (&base)[kMfmaChains], const int (&koff)[9],
+                                           int groups, int gstride, f4 (&acc)[kMfmaChains]) {
+  switch (nc) {
+    case 1: mfma_chains<1>(alds, wbl, base, koff, groups, gstride, acc); break;
+    case 2: mfma_chains<2>(alds, wbl, base, koff, groups, gstride, acc); break;
+    default: mfma_chains<kMfmaChains>(alds, wbl, base, koff, groups, gstride, acc); break;
+  }
+}
+
+// Four waves per SIMD is what the LDS of a conv2-sized plane admits; without
+// that bound the compiler spends registers on hoisted loads and halves it.
+// The deep-staging bwd_data build (planes of more than 1024 cells) would
+// spill under it and gets two.
+//
+// Forward. M = positions grouped by pool window: tile t, row r is window
+// 4t + (r>>2), sub-position r&3 (row-major, the numbering of the argmax
+// byte), so a lane's four accumulators are one window and ReLU, max and
+// argmax stay inside the lane. N = the 16 output channels, K = CIN*9.
+// LDS: [CIN][cs] halo-padded input + [K][16] weights + [tiles*16] row table.
+template <int PF, bool VEC>
+__global__ void __launch_bounds__(kBlock, 4) conv3x3_relu_pool_fwd_mfma_kernel(
+    const float* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias,
+    float* __restrict__ out, uint8_t* __restrict__ argmax, int N, int CIN, int H, int W,
+    int in_vec_flag) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int COUT = 16;
+  const bool in_vec = VEC || in_vec_flag;
+  const PlaneGeom pg = plane_geom(H, W);
+  const int PH = H / 2, PW = W / 2;
+  const int pcells = PH * PW;
+  const int ocells = COUT * pcells;
+  const int tiles = (pcells + 3) / 4;
+  const int K = CIN * 9;
+  float* ilds = (float*)smem; // [CIN][cs]
+  float* wb = ilds + CIN * pg.cs; // [K][COUT]
+  int* tb = (int*)(wb + K * COUT); // [tiles][16] top-left offset of a row's 3x3 stencil
+
+  const int plane = CIN * H * W;
+  const int npieces = plane / 4;
+
+  PlaneStage<PF> st;
+  st.init(npieces, H, W, pg);
+  int n = blockIdx.x; // the launcher guarantees gridDim.x <= N
+  st.load(in + (int64_t)n * plane, npieces, in_vec);
+
+  for (int i = threadIdx.x; i < K * COUT; i += kBlock) wb[i] = w[(i & 15) * K + (i >> 4)];
+  for (int i = threadIdx.x; i < tiles * 16; i += kBlock) {
+    const int win = i >> 2, sub = i & 3;
+    int base = 0; // rows past the last window read in bounds and store nothing
+    if (win < pcells) {
+      const int py = win / PW, px = win - py * PW;
+      base = (2 * py + (sub >> 1)) * pg.PADW + 2 * px + (sub & 1);
+    }
+    tb[i] = base;
+  }
+  for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f; // halo, once
+  __syncthreads();
+  st.store(in + (int64_t)n * plane, ilds, npieces, in_vec, H, W, pg);
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int quad = lane >> 4, co = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int cnt = (tiles - wave + 3) >> 2; // tiles wave, wave + 4, ... below `tiles`
+  int koff[9];
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int k = 4 * s + quad, ci = k / 9, tap = k - 9 * ci;
+    koff[s] = ci * pg.cs + (tap / 3) * pg.PADW + tap % 3;
+  }
+  const float bz = bias[co];
+  const float* wbl = wb + lane;
+
+  for (; n < N; n += gridDim.x) {
+    const int nn = n + gridDim.x;
+    float* outn = out + (int64_t)n * ocells + co * pcells;
+    uint8_t* argn = argmax + (int64_t)n * ocells + co * pcells;
+
+    for (int j = 0; j < cnt; j += kMfmaChains) {
+      const int nc = min(kMfmaChains, cnt - j);
+      int base[kMfmaChains];
+      f4 acc[kMfmaChains];
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        base[i] = tb[(wave + 4 * (j + min(i, nc - 1))) * 16 + co];
+        acc[i] = f4{bz, bz, bz, bz};
+      }
+      mfma_tiles(nc, ilds, wbl, base, koff, CIN / 4, 4 * pg.cs, acc);
+
+      // relu + 2x2 max of the lane's window; first index wins ties
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        const int win = 4 * (wave + 4 * (j + i)) + quad;
+        if (i < nc && win < pcells) {
+          const float r0 = fmaxf(acc[i].x, 0.0f);
+          const float r1 = fmaxf(acc[i].y, 0.0f);
+          const float r2 = fmaxf(acc[i].z, 0.0f);
+          const float r3 = fmaxf(acc[i].w, 0.0f);
+          float m = r0;
+          int arg = 0;
+          if (r1 > m) { m = r1; arg = 1; }
+          if (r2 > m) { m = r2; arg = 2; }
+          if (r3 > m) { m = r3; arg = 3; }
+          if (!(m > 0.0f)) arg |= kGateBit;
+          outn[win] = m;
+          argn[win] = (uint8_t)arg;
+        }
+      }
+    }
+    __syncthreads(); // math done: ilds may be overwritten
+
+    if (nn < N) {
+      st.load(in + (int64_t)nn * plane, npieces, in_vec);
+      st.store(in + (int64_t)nn * plane, ilds, npieces, in_vec, H, W, pg);
+    }
+    __syncthreads(); // next plane published
+  }
+}
+
+// bwd_data. M = din positions in linear order y*W + x, N = the input
+// channels (columns past CIN carry zero weights and are not stored),
+// K = COUT*9 = 144. A lane's four accumulators are four consecutive
+// positions of one channel; H*W is a multiple of 4, so they lie inside the
+// channel and go out as one 16-byte store when din allows it
+// (din_align: 2 = 16-byte, 1 = 8-byte, 0 = scalar stores).
+// LDS: [COUT][cs] padded dconv + [K][16] weights + [tiles*16] row table.
+template <int PF, bool VEC>
+__global__ void __launch_bounds__(kBlock, PF == 1 ? 4 : 2) conv3x3_relu_pool_bwd_data_mfma_kernel(
+    const float* __restrict__ dpooled, const uint8_t* __restrict__ argmax,
+    const float* __restrict__ w, float* __restrict__ din, int N, int CIN, int H, int W,
+    int cell_vec_flag, int din_align_flag) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int COUT = 16, K = COUT * 9;
+  const bool cell_vec = VEC || cell_vec_flag;
+  const int din_align = VEC ? 2 : din_align_flag;
+  const PlaneGeom pg = plane_geom(H, W);
+  const int HW = H * W;
+  const int tiles = (HW + 15) / 16;
+  float* dclds = (float*)smem; // [COUT][cs]
+  float* wb = dclds + COUT * pg.cs; // [K][16]
+  int* tb = (int*)(wb + K * 16); // [tiles][16] padded offset of position (y, x)
+
+  const int PH = H / 2, PW = W / 2;
+  const int pcells = PH * PW;
+  const int cells = COUT * pcells;
+
+  // code = LDS offset of the top-left position of the cell's 2x2 window
+  auto code_of = [&](int cell) {
+    const int co = cell / pcells;
+    const int rem = cell - co * pcells;
+    const int py = rem / PW, px = rem - py * PW;
+    return co * pg.cs + (2 * py + 1) * pg.PADW + (2 * px + 1);
+  };
+  auto put = [&](int code, float g, uint32_t a) {
+    const float v = (a & kGateBit) ? 0.0f : g;
+    const uint32_t sub = a & 3u;
+    dclds[code] = (sub == 0) ? v : 0.0f;
+    dclds[code + 1] = (sub == 1) ? v : 0.0f;
+    dclds[code + pg.PADW] = (sub == 2) ? v : 0.0f;
+    dclds[code + pg.PADW + 1] = (sub == 3) ? v : 0.0f;
+  };
+
+  CellStage<PF> st;
+  st.init(cells, code_of);
+  int n = blockIdx.x; // the launcher guarantees gridDim.x <= N
+  st.load(dpooled + (int64_t)n * cells, argmax + (int64_t)n * cells, cells, cell_vec);
+
+  for (int i = threadIdx.x; i < K * 16; i += kBlock) {
+    const int k = i >> 4, ci = i & 15;
+    const int co = k / 9, tap = k - 9 * co;
+    wb[i] = (ci < CIN) ? w[(co * CIN + ci) * 9 + tap] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < tiles * 16; i += kBlock) {
+    int base = 0; // rows past the last position read in bounds and store nothing
+    if (i < HW) {
+      const int y = i / W;
+      base = y * pg.PADW + (i - y * W);
+    }
+    tb[i] = base;
+  }
+  for (int i = threadIdx.x; i < COUT * pg.cs; i += kBlock) dclds[i] = 0.0f; // halo, once
+  __syncthreads();
+  st.store(dpooled + (int64_t)n * cells, argmax + (int64_t)n * cells, cells, cell_vec, code_of,
+           put);
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int quad = lane >> 4, ci = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int cnt = (tiles - wave + 3) >> 2; // tiles wave, wave + 4, ... below `tiles`
+  // din(y,x) += w[ky][kx] * dconv(y-ky+1, x-kx+1): padded (y-ky+2, x-kx+2)
+  int koff[9];
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int k = 4 * s + quad, co = k / 9, tap = k - 9 * co;
+    koff[s] = co * pg.cs + (2 - tap / 3) * pg.PADW + (2 - tap % 3);
+  }
+  const float* wbl = wb + lane;
+
+  for (; n < N; n += gridDim.x) {
+    const int nn = n + gridDim.x;
+    float* dinn = din + ((int64_t)n * CIN + ci) * HW;
+
+    for (int j = 0; j < cnt; j += kMfmaChains) {
+      const int nc = min(kMfmaChains, cnt - j);
+      int base[kMfmaChains];
+      f4 acc[kMfmaChains];
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        base[i] = tb[(wave + 4 * (j + min(i, nc - 1))) * 16 + ci];
+        acc[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+      mfma_tiles(nc, dclds, wbl, base, koff, COUT / 4, 4 * pg.cs, acc);
+
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        const int p0 = 16 * (wave + 4 * (j + i)) + 4 * quad;
+        if (i < nc && p0 < HW && ci < CIN) {
+          float* d = dinn + p0;
+          if (din_align == 2) {
+            *(f4*)d = acc[i];
+          } else if (din_align == 1) {
+            *(f2*)d = f2{acc[i].x, acc[i].y};
+            *(f2*)(d + 2) = f2{acc[i].z, acc[i].w};
+          } else {
+            d[0] = acc[i].x;
+            d[1] = acc[i].y;
+            d[2] = acc[i].z;
+            d[3] = acc[i].w;
+          }
+        }
+      }
+    }
+    __syncthreads(); // math done: dclds may be overwritten
+    if (nn < N) {
+      st.load(dpooled + (int64_t)nn * cells, argmax + (int64_t)nn * cells, cells, cell_vec);
+      st.store(dpooled + (int64_t)nn * cells, argmax + (int64_t)nn * cells, cells, cell_vec,
+               code_of, put);
+    }
+    __syncthreads();
+  }
+}
+
 // ----------------------------------------------------------- bwd weight
 
 // Workgroup = chunk of `samples` samples looped through LDS. The pool
@@ -710,6 +1006,14 @@ static bool cells_vectorizable(const at::Tensor& dpooled, const at::Tensor& argm
 // what 4 * kBlock pieces do not cover is copied piece by piece
 static int stage_depth(int pieces) { return pieces <= kBlock ? 1 : 4; }
 
+// Shapes that forward and bwd_data run as an f32 MFMA implicit GEMM.
+// DMLCLOUD_SMALLCNN_MFMA=0 (read per call) forces the VALU kernels.
+static bool mfma_eligible(int CIN, int COUT) {
+  if (COUT != 16 || CIN % 4 != 0 || CIN > 16) return false;
+  const char* env = std::getenv("DMLCLOUD_SMALLCNN_MFMA");
+  return env == nullptr || atoi(env) != 0;
+}
+
 void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor out,
                            at::Tensor argmax) {
   TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kFloat && in.is_contiguous(),
@@ -734,6 +1038,18 @@ void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor
   const int blocks = std::min(N, kMaxGrid);
   const int in_vec = aligned_to(in.data_ptr(), 16);
   const bool deep = stage_depth(CIN * H * W / 4) > 1;
+  const int gemm_tiles = ((H / 2) * (W / 2) + 3) / 4;
+  const int mfma_lds = (CIN * pg.cs + COUT * CIN * 9 + gemm_tiles * 16) * (int)sizeof(float);
+  if (mfma_eligible(CIN, COUT) && mfma_lds <= kMaxLds) {
+    auto kernel = in_vec ? (deep ? conv3x3_relu_pool_fwd_mfma_kernel<4, true>
+                                 : conv3x3_relu_pool_fwd_mfma_kernel<1, true>)
+                         : (deep ? conv3x3_relu_pool_fwd_mfma_kernel<4, false>
+                                 : conv3x3_relu_pool_fwd_mfma_kernel<1, false>);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), mfma_lds, stream,
+                       in.data_ptr<float>(), w.data_ptr<float>(), b.data_ptr<float>(),
+                       out.data_ptr<float>(), argmax.data_ptr<uint8_t>(), N, CIN, H, W, in_vec);
+    return;
+  }
   auto kernel = in_vec ? (deep ? conv3x3_relu_pool_fwd_kernel<4, true>
                                : conv3x3_relu_pool_fwd_kernel<1, true>)
                        : (deep ? conv3x3_relu_pool_fwd_kernel<4, false>
@@ -763,6 +1079,20 @@ void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tenso
   const int cell_vec = cells_vectorizable(dpooled, argmax, cells);
   const int din_vec = aligned_to(din.data_ptr(), 8);
   const bool deep = stage_depth((cells + 3) / 4) > 1;
+  const int gemm_tiles = (H * W + 15) / 16;
+  const int mfma_lds = (COUT * pg.cs + COUT * 9 * 16 + gemm_tiles * 16) * (int)sizeof(float);
+  if (mfma_eligible(CIN, COUT) && mfma_lds <= kMaxLds) {
+    const int din_align = aligned_to(din.data_ptr(), 16) ? 2 : din_vec;
+    auto kernel = (cell_vec && din_align == 2)
+                      ? (deep ? conv3x3_relu_pool_bwd_data_mfma_kernel<4, true>
+                              : conv3x3_relu_pool_bwd_data_mfma_kernel<1, true>)
+                      : (deep ? conv3x3_relu_pool_bwd_data_mfma_kernel<4, false>
+                              : conv3x3_relu_pool_bwd_data_mfma_kernel<1, false>);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), mfma_lds, stream,
+                       dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(), w.data_ptr<float>(),
+                       din.data_ptr<float>(), N, CIN, H, W, cell_vec, din_align);
+    return;
+  }
   auto kernel = (cell_vec && din_vec) ? (deep ? conv3x3_relu_pool_bwd_data_kernel<4, true>
                                               : conv3x3_relu_pool_bwd_data_kernel<1, true>)
                                       : (deep ? conv3x3_relu_pool_bwd_data_kernel<4, false>

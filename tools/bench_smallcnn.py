@@ -1,8 +1,10 @@
 """Micro-benchmark of the fused smallcnn kernels per layer shape.
 
-Run on a GPU box:  python tools/bench_smallcnn.py [batch ...]
+Run on a GPU box:  python tools/bench_smallcnn.py [--no-torch] [batch ...]
 Prints per-kernel times (cuda events, 100 reps) for the two MNIST-CNN
-layer shapes, plus the torch/MIOpen equivalents for comparison.
+layer shapes, plus the torch/MIOpen equivalents for comparison (left out
+with --no-torch). Shapes that take the f32 MFMA path get a second row with
+DMLCLOUD_SMALLCNN_MFMA=0, the VALU kernels.
 """
 
 import os
@@ -32,7 +34,8 @@ def time_fn(fn, reps=100, warmup=20):
     return start.elapsed_time(end) / reps * 1e3  # us
 
 
-def bench_shape(n, cin, cout, hw):
+def bench_shape(n, cin, cout, hw, with_torch=True, mfma=True):
+    os.environ['DMLCLOUD_SMALLCNN_MFMA'] = '1' if mfma else '0'  # read per call
     torch.manual_seed(0)
     x = torch.randn(n, cin, hw, hw, device=DEV)
     w = torch.randn(cout, cin, 3, 3, device=DEV) * 0.1
@@ -48,6 +51,16 @@ def bench_shape(n, cin, cout, hw):
     t_fwd = time_fn(lambda: _C.conv3x3_relu_pool_fwd(x, w, b, pooled, argmax))
     t_bwdd = time_fn(lambda: _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, w, din))
     t_bwdw = time_fn(lambda: _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db))
+
+    os.environ.pop('DMLCLOUD_SMALLCNN_MFMA')
+    line = (
+        f'N={n:6d} cin={cin:2d} cout={cout:2d} hw={hw:2d} mfma={int(mfma)} | '
+        f'fwd {t_fwd:8.1f}us bwd_data {t_bwdd:8.1f}us bwd_w {t_bwdw:8.1f}us '
+        f'(sum {t_fwd + t_bwdd + t_bwdw:8.1f}us)'
+    )
+    if not with_torch:
+        print(line)
+        return
 
     # torch eager equivalents
     def torch_fwd():
@@ -67,15 +80,14 @@ def bench_shape(n, cin, cout, hw):
     t_tfwd = time_fn(torch_fwd, reps=50)
     t_tfb = time_fn(torch_fwdbwd, reps=50)
 
-    print(
-        f'N={n:6d} cin={cin:2d} cout={cout:2d} hw={hw:2d} | '
-        f'fwd {t_fwd:8.1f}us bwd_data {t_bwdd:8.1f}us bwd_w {t_bwdw:8.1f}us '
-        f'(sum {t_fwd + t_bwdd + t_bwdw:8.1f}us) | torch fwd {t_tfwd:8.1f}us fwd+bwd {t_tfb:8.1f}us'
-    )
+    print(f'{line} | torch fwd {t_tfwd:8.1f}us fwd+bwd {t_tfb:8.1f}us')
 
 
 if __name__ == '__main__':
-    batches = [int(a) for a in sys.argv[1:]] or [1024, 4096, 16384]
+    args = sys.argv[1:]
+    with_torch = '--no-torch' not in args
+    batches = [int(a) for a in args if not a.startswith('--')] or [1024, 4096, 16384]
     for n in batches:
-        bench_shape(n, 1, 16, 28)  # conv1 shape
-        bench_shape(n, 16, 16, 14)  # conv2 shape
+        bench_shape(n, 1, 16, 28, with_torch)  # conv1 shape
+        bench_shape(n, 16, 16, 14, with_torch)  # conv2 shape
+        bench_shape(n, 16, 16, 14, False, mfma=False)  # conv2 shape, VALU kernels

@@ -1,5 +1,10 @@
 """Tiny workload for rocprofv3 --pmc counter collection: runs each fused
-smallcnn kernel and the metric reducer a handful of times (small DB)."""
+smallcnn kernel and the metric reducer a handful of times (small DB).
+
+    python tools/pmc_probe.py [batch] [--smallcnn-only]
+
+batch defaults to 4096. DMLCLOUD_SMALLCNN_MFMA=0 in the environment puts the
+conv2 shape on the VALU kernels."""
 
 import os
 import sys
@@ -14,7 +19,8 @@ DEV = 'cuda:0'
 
 
 def main():
-    n = 4096
+    args = sys.argv[1:]
+    n = next((int(a) for a in args if not a.startswith('--')), 4096)
     torch.manual_seed(0)
     for cin, cout, hw in [(1, 16, 28), (16, 16, 14)]:
         x = torch.randn(n, cin, hw, hw, device=DEV)
@@ -30,6 +36,11 @@ def main():
             _C.conv3x3_relu_pool_fwd(x, w, b, pooled, argmax)
             _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, w, din)
             _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db)
+
+    if '--smallcnn-only' in args:
+        torch.cuda.synchronize()
+        print('pmc probe done')
+        return
 
     v = torch.randn(1 << 22, device=DEV)
     acc = torch.zeros(1, dtype=torch.float64, device=DEV)
