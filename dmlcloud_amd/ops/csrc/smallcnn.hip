@@ -23,6 +23,11 @@
 //   v6  (this file) conv2-like layers run fwd and bwd_data as f32 MFMA
 //       implicit GEMMs, bit for bit the VALU kernels' results
 //       (profiles/smallcnn_mfma.md); see "f32 MFMA forms" below.
+//   v7  conv2 bwd_weight (COUT == CIN == 16) is an f32 MFMA implicit GEMM
+//       too: the dense form of the pool gradient does 4x the gather's
+//       multiplications and is still faster, bit for bit the VALU
+//       kernel's chains (profiles/smallcnn_bwdw_mfma.md); see
+//       conv3x3_relu_pool_bwd_weight_mfma_kernel.
 //   v5  data-movement pass, arithmetic untouched
 //       (profiles/smallcnn_pipelined.md):
 //       - the ReLU gate travels in bit 2 of the argmax byte, so neither
@@ -957,6 +962,202 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
   }
 }
 
+// bwd_weight as an f32 MFMA implicit GEMM, COUT == CIN == 16 only: there the
+// VALU kernel above has pairs == kBlock and one slice, so every (co, ci, tap)
+// is ONE serial fmaf chain over (the workgroup's sample sequence, cells in
+// ascending order), and this kernel runs the same chains:
+//
+//   D_tap[co][ci] += sum_k A[co][k] * B_tap[k][ci],   k = 4 * cell + sub
+//   A[co][k]     = pre-gated gradient of (co, cell) if sub is the argmax
+//                  position, else +0.0f
+//   B_tap[k][ci] = padded_in[ci][2py + (sub>>1) + ky][2px + (sub&1) + kx]
+//
+// One v_mfma_f32_16x16x4_f32 step is one pooled window; lane quad = lane>>4
+// is the sub-position, lane&15 is co for A and ci for B, and a lane's four
+// accumulators are D[4*quad .. +3][lane&15]. The dense form does 4x the
+// VALU kernel's multiplications, three of four with a zero: 441 MFMAs per
+// sample against 11 ds_read_b32 per 9 FMAs in the gather, which is what
+// bound the VALU kernel (profiles/smallcnn_bwdw_mfma.md).
+//
+// Work is split over waves by tap, never by k: unit u = 0..3 owns taps u,
+// u + 4, u + 8 (3/2/2/2) for the whole workgroup, as independent accumulator
+// chains sharing A (rotating the three-tap unit over the waves with the
+// workgroup index measured no different). db is the VALU kernel's `accb += g` chain, run by unit 1
+// on the gradient it has read anyway. Chunking, the sequence of samples,
+// the `part` row and the reduce kernel are those of the VALU kernel.
+//
+// The added zeros are fmaf(+0, x, acc), which returns acc for finite x and
+// non-zero acc. Two differences from the VALU kernel remain, neither
+// reachable from finite training data:
+//   - a chain whose running value is -0.0 becomes +0.0 (only the sign of a
+//     zero result changes);
+//   - a non-finite input gives NaN at positions the sparse kernel never
+//     multiplied, as torch's dense conv backward does.
+//
+// LDS: [16][cs] halo-padded input in a geometry of its own (no vector reads
+// here, so no alignment padding: PADW = W + 2, and cs/2 odd puts the 32
+// lanes of a ds_read_b32 group, 16 channels x 2 adjacent columns, on 32
+// banks) + [16][ps] (gradient, sub) pairs, read as one b64 per window that
+// the four quads share (ps odd: 16 channels on 16 distinct bank pairs).
+// A word of B is (per-lane constant) + (wave-uniform window and tap offset):
+// the sample loop has no table and no division.
+
+__host__ __device__ __forceinline__ PlaneGeom bwdw_mfma_geom(int H, int W) {
+  PlaneGeom g;
+  g.PADH = H + 2;
+  g.PADW = W + 2;
+  g.cs = g.PADH * g.PADW; // even, as H and W are
+  if ((g.cs & 2) == 0) g.cs += 2;
+  return g;
+}
+
+__host__ __device__ __forceinline__ int bwdw_mfma_pstride(int pcells) { return pcells | 1; }
+
+// One sample: the wave's NT tap chains (and the db chain) over all windows.
+// The operands of window s + 1 are read before the MFMAs of window s.
+template <int NT, bool DB>
+__device__ __forceinline__ void bwdw_mfma_sample(const float* __restrict__ bl,
+                                                 const f2* __restrict__ al, const int (&toff)[3],
+                                                 int PH, int PW, int PADW, int quad,
+                                                 f4 (&acc)[3], float& accb) {
+  const int pcells = PH * PW;
+  f2 gs = al[0];
+  float b[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) b[i] = bl[toff[i]];
+  int px = 0, rowoff = 0; // wave-uniform
+  for (int cell = 0; cell < pcells; ++cell) {
+    const f2 gs0 = gs;
+    float b0[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) b0[i] = b[i];
+    if (++px == PW) {
+      px = 0;
+      rowoff += 2 * PADW;
+    }
+    if (cell + 1 < pcells) {
+      gs = al[cell + 1];
+      const float* bp = bl + rowoff + 2 * px;
+#pragma unroll
+      for (int i = 0; i < NT; ++i) b[i] = bp[toff[i]];
+    }
+    const float a = (__float_as_int(gs0.y) == quad) ? gs0.x : 0.0f;
+    if (DB) accb += gs0.x;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0[i], acc[i], 0, 0, 0);
+    }
+  }
+}
+
+// Four waves per SIMD, except the build that stages both operands deep
+// (planes of more than 1024 cells), which would spill under that bound.
+template <int PFI, int PFC, bool VEC>
+__global__ void __launch_bounds__(kBlock, (PFI > 1 && PFC > 1) ? 2 : 4)
+conv3x3_relu_pool_bwd_weight_mfma_kernel(
+    const float* __restrict__ dpooled, const uint8_t* __restrict__ argmax,
+    const float* __restrict__ in, float* __restrict__ part, int N, int H, int W, int samples,
+    int in_vec_flag, int cell_vec_flag) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int CIN = 16, COUT = 16;
+  const bool in_vec = VEC || in_vec_flag, cell_vec = VEC || cell_vec_flag;
+  const PlaneGeom pg = bwdw_mfma_geom(H, W);
+  const int iplane = CIN * H * W;
+  const int npieces = iplane / 4;
+  const int PH = H / 2, PW = W / 2;
+  const int pcells = PH * PW;
+  const int ps = bwdw_mfma_pstride(pcells);
+  float* ilds = (float*)smem; // [CIN][cs]
+  f2* alds = (f2*)(ilds + CIN * pg.cs); // [COUT][ps] (pre-gated gradient, sub)
+  const int cells = COUT * pcells;
+
+  auto code_of = [&](int cell) {
+    const int cco = cell / pcells;
+    return cco * ps + (cell - cco * pcells);
+  };
+  auto put = [&](int code, float g, uint32_t a) {
+    alds[code] = f2{(a & kGateBit) ? 0.0f : g, __int_as_float((int)(a & 3u))};
+  };
+
+  // chunk blockIdx.x and, when the grid was capped, every gridDim.x-th
+  // chunk after it; all chunks of a workgroup share its accumulators
+  const int nchunks = (N + samples - 1) / samples;
+  int chunk = blockIdx.x; // the launcher guarantees gridDim.x <= nchunks
+  int64_t n = (int64_t)chunk * samples;
+  int64_t nend = min((int64_t)N, n + samples);
+
+  PlaneStage<PFI> sti;
+  CellStage<PFC> stc;
+  sti.init(npieces, H, W, pg);
+  stc.init(cells, code_of);
+  sti.load(in + n * iplane, npieces, in_vec);
+  stc.load(dpooled + n * cells, argmax + n * cells, cells, cell_vec);
+
+  // zero the input halo ONCE; interiors are overwritten every sample
+  for (int i = threadIdx.x; i < CIN * pg.cs; i += kBlock) ilds[i] = 0.0f;
+  __syncthreads();
+  sti.store(in + n * iplane, ilds, npieces, in_vec, H, W, pg);
+  stc.store(dpooled + n * cells, argmax + n * cells, cells, cell_vec, code_of, put);
+  __syncthreads();
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int quad = lane >> 4, col = lane & 15; // col: co of A, ci of B and D
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int unit = wave; // one owner per accumulator, sample-invariant addresses
+  int toff[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int tap = min(unit + 4 * i, 8);
+    toff[i] = (tap / 3) * pg.PADW + tap % 3;
+  }
+  const float* bl = ilds + col * pg.cs + (quad >> 1) * pg.PADW + (quad & 1);
+  const f2* al = alds + col * ps;
+
+  f4 acc[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) acc[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+  float accb = 0.0f;
+
+  bool more = true;
+  while (more) {
+    // successor of sample n in this workgroup's sequence
+    int64_t nn = n + 1;
+    if (nn >= nend) {
+      chunk += gridDim.x;
+      nn = (int64_t)chunk * samples;
+      nend = min((int64_t)N, nn + samples);
+      more = chunk < nchunks;
+    }
+    if (unit == 0) {
+      bwdw_mfma_sample<3, false>(bl, al, toff, PH, PW, pg.PADW, quad, acc, accb);
+    } else if (unit == 1) {
+      bwdw_mfma_sample<2, true>(bl, al, toff, PH, PW, pg.PADW, quad, acc, accb);
+    } else {
+      bwdw_mfma_sample<2, false>(bl, al, toff, PH, PW, pg.PADW, quad, acc, accb);
+    }
+    __syncthreads(); // math done: the staging regions may be overwritten
+    if (more) {
+      sti.load(in + nn * iplane, npieces, in_vec);
+      stc.load(dpooled + nn * cells, argmax + nn * cells, cells, cell_vec);
+      sti.store(in + nn * iplane, ilds, npieces, in_vec, H, W, pg);
+      stc.store(dpooled + nn * cells, argmax + nn * cells, cells, cell_vec, code_of, put);
+    }
+    __syncthreads();
+    n = nn;
+  }
+
+  float* row = part + (int64_t)blockIdx.x * (COUT * CIN * 9 + COUT);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int tap = unit + 4 * i;
+    if (tap < 9) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row[((4 * quad + j) * CIN + col) * 9 + tap] = acc[i][j];
+    }
+  }
+  if (unit == 1 && quad == 0) row[COUT * CIN * 9 + col] = accb;
+}
+
 // Sums the `rows` partial rows of `part` [rows][cols] column by column in a
 // fixed order and STORES the totals to dw (cols < ndw) / db (the rest; may
 // be null), which need not be initialised. Workgroup = kRedCols columns x
@@ -1006,7 +1207,8 @@ static bool cells_vectorizable(const at::Tensor& dpooled, const at::Tensor& argm
 // what 4 * kBlock pieces do not cover is copied piece by piece
 static int stage_depth(int pieces) { return pieces <= kBlock ? 1 : 4; }
 
-// Shapes that forward and bwd_data run as an f32 MFMA implicit GEMM.
+// Shapes that forward and bwd_data run as an f32 MFMA implicit GEMM
+// (bwd_weight: CIN == 16 among them only).
 // DMLCLOUD_SMALLCNN_MFMA=0 (read per call) forces the VALU kernels.
 static bool mfma_eligible(int CIN, int COUT) {
   if (COUT != 16 || CIN % 4 != 0 || CIN > 16) return false;
@@ -1142,6 +1344,30 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
   const int in_vec = aligned_to(in.data_ptr(), 16);
   const int cell_vec = cells_vectorizable(dpooled, argmax, cells);
   const int pfi = stage_depth(CIN * H * W / 4), pfc = stage_depth((cells + 3) / 4);
+  // COUT == CIN == 16 is the one shape whose VALU chains are whole per
+  // (co, ci, tap), which the MFMA form reproduces bit for bit
+  const int mfma_lds = (CIN * bwdw_mfma_geom(H, W).cs + 2 * COUT * bwdw_mfma_pstride(pcells)) *
+                       (int)sizeof(float);
+  if (CIN == 16 && mfma_eligible(CIN, COUT) && mfma_lds <= kMaxLds) {
+    auto mkernel =
+        (in_vec && cell_vec)
+            ? (pfi == 1 ? (pfc == 1 ? conv3x3_relu_pool_bwd_weight_mfma_kernel<1, 1, true>
+                                    : conv3x3_relu_pool_bwd_weight_mfma_kernel<1, 4, true>)
+                        : (pfc == 1 ? conv3x3_relu_pool_bwd_weight_mfma_kernel<4, 1, true>
+                                    : conv3x3_relu_pool_bwd_weight_mfma_kernel<4, 4, true>))
+            : (pfi == 1 ? (pfc == 1 ? conv3x3_relu_pool_bwd_weight_mfma_kernel<1, 1, false>
+                                    : conv3x3_relu_pool_bwd_weight_mfma_kernel<1, 4, false>)
+                        : (pfc == 1 ? conv3x3_relu_pool_bwd_weight_mfma_kernel<4, 1, false>
+                                    : conv3x3_relu_pool_bwd_weight_mfma_kernel<4, 4, false>));
+    hipLaunchKernelGGL(mkernel, dim3(blocks), dim3(kBlock), mfma_lds, stream,
+                       dpooled.data_ptr<float>(), argmax.data_ptr<uint8_t>(),
+                       in.data_ptr<float>(), part.data_ptr<float>(), N, H, W, samples, in_vec,
+                       cell_vec);
+    hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((cols + kRedCols - 1) / kRedCols),
+                       dim3(kBlock), 0, stream, part.data_ptr<float>(), dw.data_ptr<float>(),
+                       db.defined() ? db.data_ptr<float>() : nullptr, blocks, cols, ndw);
+    return;
+  }
   auto kernel =
       (in_vec && cell_vec)
           ? (pfi == 1 ? (pfc == 1 ? conv3x3_relu_pool_bwd_weight_kernel<1, 1, true>
