@@ -47,6 +47,9 @@ void conv3x3_relu_pool_bwd_data(at::Tensor dpooled, at::Tensor argmax, at::Tenso
                                 at::Tensor din);
 void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Tensor in,
                                   at::Tensor dw, at::Tensor db);
+void conv3x3_relu_pool_bwd_data_weight(at::Tensor dpooled2, at::Tensor argmax2, at::Tensor w2,
+                                       at::Tensor argmax1, at::Tensor x, at::Tensor dw1,
+                                       at::Tensor db1);
 
 // layernorm.hip
 void layernorm_fwd(at::Tensor x, at::Tensor gamma, at::Tensor beta, at::Tensor y,
@@ -97,6 +100,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused conv+relu+pool input gradient");
   m.def("conv3x3_relu_pool_bwd_weight", &dmlamd::conv3x3_relu_pool_bwd_weight,
         "Fused conv+relu+pool weight/bias gradient");
+  m.def("conv3x3_relu_pool_bwd_data_weight", &dmlamd::conv3x3_relu_pool_bwd_data_weight,
+        "Layer-2 input gradient and layer-1 weight/bias gradient of a two-layer "
+        "conv+relu+pool stack in one kernel (no din tensor)");
   m.def("layernorm_fwd", &dmlamd::layernorm_fwd, "Fused bf16 LayerNorm forward (row per wave)");
   m.def("layernorm_bwd", &dmlamd::layernorm_bwd,
         "Fused bf16 LayerNorm backward (dx + dgamma/dbeta)");

@@ -28,6 +28,12 @@
 //       multiplications and is still faster, bit for bit the VALU
 //       kernel's chains (profiles/smallcnn_bwdw_mfma.md); see
 //       conv3x3_relu_pool_bwd_weight_mfma_kernel.
+//   v8  conv2 bwd_data and conv1 bwd_weight are one kernel when conv1 needs
+//       no input gradient: conv2's din, whose only reader was conv1
+//       bwd_weight, goes from the MFMA accumulators through LDS into the
+//       gather and never to memory, bit for bit the two kernels
+//       (profiles/smallcnn_bwd_merged.md); see
+//       conv3x3_relu_pool_bwd_data_weight_kernel.
 //   v5  data-movement pass, arithmetic untouched
 //       (profiles/smallcnn_pipelined.md):
 //       - the ReLU gate travels in bit 2 of the argmax byte, so neither
@@ -807,6 +813,44 @@ __global__ void __launch_bounds__(kBlock, PF == 1 ? 4 : 2) conv3x3_relu_pool_bwd
 
 // ----------------------------------------------------------- bwd weight
 
+// End of a gather workgroup: the nslices partials of every (pair, tap) and
+// of db are summed through LDS in ascending slice order (skipped when there
+// is one slice), and slice 0 writes the workgroup's row of `part`. The
+// caller has a barrier behind its last use of redlds' memory.
+__device__ __forceinline__ void bwdw_finish_row(float (&acc)[9], float accb,
+                                                float* __restrict__ redlds,
+                                                float* __restrict__ part, int pairs, int nslices,
+                                                int pair, int slice, int co, int ci, int COUT,
+                                                bool active) {
+  if (nslices > 1) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      redlds[threadIdx.x] = active ? acc[k] : 0.0f;
+      __syncthreads();
+      if (active && slice == 0) {
+        float total = acc[k];
+        for (int sl = 1; sl < nslices; ++sl) total += redlds[sl * pairs + pair];
+        acc[k] = total;
+      }
+      __syncthreads();
+    }
+    redlds[threadIdx.x] = (active && ci == 0) ? accb : 0.0f;
+    __syncthreads();
+    if (active && slice == 0 && ci == 0) {
+      float total = accb;
+      for (int sl = 1; sl < nslices; ++sl) total += redlds[sl * pairs + pair];
+      accb = total;
+    }
+  }
+
+  if (active && slice == 0) {
+    float* row = part + (int64_t)blockIdx.x * (pairs * 9 + COUT);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) row[pair * 9 + k] = acc[k];
+    if (ci == 0) row[pairs * 9 + co] = accb;
+  }
+}
+
 // Workgroup = chunk of `samples` samples looped through LDS. The pool
 // gradient is pre-gated at stage time into dense per-cell (g, offset) pairs
 // (g = 0 encodes "no gradient"). Thread owns ((co,ci), slice): 9 register
@@ -932,34 +976,7 @@ __global__ void __launch_bounds__(kBlock) conv3x3_relu_pool_bwd_weight_kernel(
     n = nn;
   }
 
-  // cross-slice reduction (skipped when nslices == 1)
-  if (nslices > 1) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      redlds[threadIdx.x] = active ? acc[k] : 0.0f;
-      __syncthreads();
-      if (active && slice == 0) {
-        float total = acc[k];
-        for (int sl = 1; sl < nslices; ++sl) total += redlds[sl * pairs + pair];
-        acc[k] = total;
-      }
-      __syncthreads();
-    }
-    redlds[threadIdx.x] = (active && ci == 0) ? accb : 0.0f;
-    __syncthreads();
-    if (active && slice == 0 && ci == 0) {
-      float total = accb;
-      for (int sl = 1; sl < nslices; ++sl) total += redlds[sl * pairs + pair];
-      accb = total;
-    }
-  }
-
-  if (active && slice == 0) {
-    float* row = part + (int64_t)blockIdx.x * (pairs * 9 + COUT);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) row[pair * 9 + k] = acc[k];
-    if (ci == 0) row[pairs * 9 + co] = accb;
-  }
+  bwdw_finish_row(acc, accb, redlds, part, pairs, nslices, pair, slice, co, ci, COUT, active);
 }
 
 // bwd_weight as an f32 MFMA implicit GEMM, COUT == CIN == 16 only: there the
@@ -1158,6 +1175,334 @@ conv3x3_relu_pool_bwd_weight_mfma_kernel(
   if (unit == 1 && quad == 0) row[COUT * CIN * 9 + col] = accb;
 }
 
+// ------------------------------------- layer-2 bwd_data + layer-1 bwd_weight
+//
+// The image layer needs no input gradient, so layer 2's din has one reader:
+// layer 1's bwd_weight, which takes it as its dpooled. This kernel computes a
+// sample's din as conv3x3_relu_pool_bwd_data_mfma_kernel does, hands it
+// through LDS to the gather of conv3x3_relu_pool_bwd_weight_kernel and ends
+// in that kernel's `part` row: din never goes to memory (12.5 KB per sample
+// written and read back at the MNIST shapes).
+//
+// Notation: layer 1 is CIN1 -> C1 on H1 x W1; layer 2 is C1 -> 16 on
+// H2 x W2 = H1/2 x W1/2, whose positions are layer 1's pooled cells.
+//
+// Bit for bit the two kernels: the MFMA phase is the bwd_data kernel's (same
+// tiles, same k order; only the accumulators' destination changes), the
+// gather is the VALU kernel's loop (thread = ((co, ci), slice), cells
+// slice, slice + nslices, ... ascending, `accb += g`, nine fmaf in tap
+// order), a workgroup's samples are the VALU kernel's sequence of chunks,
+// and the cross-slice sum and the `part` row are shared code.
+//
+// A lane's four accumulators are four consecutive cells of channel ci. The
+// gather's chain walks one cell per tile over tiles of all four waves, so
+// the hand-over goes through LDS, and through dclds itself: din(n) has the
+// geometry of dconv(n), which is dead once every tile of the sample is done,
+// so din is written over the INTERIOR of dclds' first C1 planes. The halo
+// stays zero and the next sample's staging rewrites the whole interior. A
+// wave keeps its (at most kMergedHold) tile accumulators across the barrier
+// behind the MFMAs; shapes with more tiles per wave are not eligible. A
+// copy of its own for din would add 12.5 KB of LDS at the MNIST shapes and
+// take the kernel from four workgroups per CU to three, where the
+// workload's 1024 workgroups no longer fit in one round.
+//
+// Layer 1's argmax bytes are staged as they are and decoded in the gather:
+// the gate (bit 2) selects +0.0f as the kernel above stores it, bits 0-1
+// the position in the window, whose top-left offset is stepped along with
+// the cell index (no division, no offset table).
+//
+// Sample loop:
+//   A  MFMA on dclds(n); barrier; accumulators -> dclds interior. x(n) and
+//      argmax1(n), loaded before the MFMAs, go to LDS behind them. barrier
+//   B  gather of n; barrier; dpooled2/argmax2 of the next sample, loaded
+//      before the gather, are expanded into dclds. barrier
+//
+// LDS: [16][cs2] padded dconv / din + [144][16] weights + [tiles*16] row
+// table + [CIN1][cs1] padded x + argmax1 bytes. The cross-slice sum reuses
+// the front of dclds.
+
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+// One sample's argmax bytes, copied to LDS unchanged. mode 2: 16-byte pieces,
+// the first PF per thread loaded together ahead of their use; mode 1: 32-bit
+// words; mode 0: bytes (the launcher picks by alignment and count).
+template <int PF>
+struct ByteStage {
+  u4 v[PF];
+
+  __device__ __forceinline__ void load(const uint8_t* __restrict__ g, int bytes, int mode) {
+    if (mode != 2) return;
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const int piece = threadIdx.x + k * kBlock;
+      if (16 * piece < bytes) v[k] = *(const u4*)(g + 16 * piece);
+    }
+  }
+  __device__ __forceinline__ void store(const uint8_t* __restrict__ g, uint8_t* __restrict__ lds,
+                                        int bytes, int mode) const {
+    if (mode == 2) {
+#pragma unroll
+      for (int k = 0; k < PF; ++k) {
+        const int piece = threadIdx.x + k * kBlock;
+        if (16 * piece < bytes) *(u4*)(lds + 16 * piece) = v[k];
+      }
+      for (int piece = threadIdx.x + PF * kBlock; 16 * piece < bytes; piece += kBlock) {
+        *(u4*)(lds + 16 * piece) = *(const u4*)(g + 16 * piece);
+      }
+    } else if (mode == 1) {
+      for (int i = threadIdx.x; 4 * i < bytes; i += kBlock) {
+        ((uint32_t*)lds)[i] = ((const uint32_t*)g)[i];
+      }
+    } else {
+      for (int i = threadIdx.x; i < bytes; i += kBlock) lds[i] = g[i];
+    }
+  }
+};
+
+constexpr int kMergedHold = kMfmaChains + 1; // tiles per wave kept in registers
+
+// The value, made opaque to the optimizer. The merged kernel runs at the
+// register limit of four waves per SIMD: what is derived from an opaque
+// value inside the sample loop (per-thread 64-bit load addresses) or behind
+// it (the roles of the final reduction) is worked out there, in a few
+// instructions, and holds no register across the MFMA phase.
+__device__ __forceinline__ int opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// Four waves per SIMD is what the LDS admits at the MNIST shapes. The build
+// that stages x deep and the builds for unaligned bases would spill under
+// that bound and get two. Layer 2's cells and the argmax1 bytes are at most
+// one 16-byte piece per thread: eligible shapes have
+// H2 * W2 <= 16 * kMergedHold = kBlock positions.
+template <int PFX, bool VEC>
+__global__ void __launch_bounds__(kBlock, (PFX > 1 || !VEC) ? 2 : 4)
+conv3x3_relu_pool_bwd_data_weight_kernel(
+    const float* __restrict__ dpooled2, const uint8_t* __restrict__ argmax2,
+    const float* __restrict__ w2, const uint8_t* __restrict__ argmax1,
+    const float* __restrict__ x, float* __restrict__ part, int N, int CIN1, int C1, int H1,
+    int W1, int samples, int x_vec_flag, int cell_vec_flag, int am1_mode_flag) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int COUT2 = 16, K = COUT2 * 9;
+  const bool x_vec = VEC || x_vec_flag, cell_vec = VEC || cell_vec_flag;
+  const int am1_mode = VEC ? 2 : am1_mode_flag;
+  const int H2 = H1 / 2, W2 = W1 / 2;
+  const PlaneGeom pg1 = plane_geom(H1, W1), pg2 = plane_geom(H2, W2);
+  const int HW2 = H2 * W2; // layer 2 positions = layer 1 pooled cells
+  const int tiles = (HW2 + 15) / 16;
+  const int xplane = CIN1 * H1 * W1;
+  const int xpieces = xplane / 4;
+  const int cells1 = C1 * HW2;
+  const int PH2 = H2 / 2, PW2 = W2 / 2;
+  const int pcells2 = PH2 * PW2;
+  const int cells2 = COUT2 * pcells2;
+
+  float* dclds = (float*)smem; // [COUT2][cs2]
+  float* wb = dclds + COUT2 * pg2.cs; // [K][16]
+  int* tb = (int*)(wb + K * 16); // [tiles][16] padded offset of position (y, x)
+  float* ilds = (float*)(tb + tiles * 16); // [CIN1][cs1]
+  uint8_t* alds = (uint8_t*)(ilds + CIN1 * pg1.cs); // [C1][HW2] argmax1 bytes
+  float* redlds = dclds; // [kBlock], after the sample loop
+
+  // layer 2 staging: as in conv3x3_relu_pool_bwd_data_mfma_kernel
+  auto code_of = [&](int cell) {
+    const int co = cell / pcells2;
+    const int rem = cell - co * pcells2;
+    const int py = rem / PW2, px = rem - py * PW2;
+    return co * pg2.cs + (2 * py + 1) * pg2.PADW + (2 * px + 1);
+  };
+  auto put = [&](int code, float g, uint32_t a) {
+    const float v = (a & kGateBit) ? 0.0f : g;
+    const uint32_t sub = a & 3u;
+    float* d = dclds + opaque(code); // the second row's address is not kept either
+    d[0] = (sub == 0) ? v : 0.0f;
+    d[1] = (sub == 1) ? v : 0.0f;
+    d[pg2.PADW] = (sub == 2) ? v : 0.0f;
+    d[pg2.PADW + 1] = (sub == 3) ? v : 0.0f;
+  };
+
+  // chunk blockIdx.x and, when the grid was capped, every gridDim.x-th
+  // chunk after it; all chunks of a workgroup share its accumulators
+  const int nchunks = (N + samples - 1) / samples;
+  int chunk = blockIdx.x; // the launcher guarantees gridDim.x <= nchunks
+  int64_t n = (int64_t)chunk * samples;
+  int64_t nend = min((int64_t)N, n + samples);
+
+  // eligible shapes: one piece per thread covers layer 2's cells and the
+  // argmax1 bytes (and x when PFX == 1), so the stagers' tail loops are dead
+  __builtin_assume(cells2 <= 4 * kBlock);
+  __builtin_assume(cells1 <= 16 * kBlock);
+  __builtin_assume(PFX > 1 || xpieces <= kBlock);
+  PlaneStage<PFX> sx;
+  CellStage<1> sc;
+  ByteStage<1> sa;
+  sx.init(xpieces, H1, W1, pg1);
+  sc.init(cells2, code_of);
+  sc.load(dpooled2 + n * cells2, argmax2 + n * cells2, cells2, cell_vec);
+
+  for (int i = threadIdx.x; i < K * 16; i += kBlock) {
+    const int k = i >> 4, c = i & 15;
+    const int co = k / 9, tap = k - 9 * co;
+    wb[i] = (c < C1) ? w2[(co * C1 + c) * 9 + tap] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < tiles * 16; i += kBlock) {
+    int base = 0; // rows past the last position read in bounds and store nothing
+    if (i < HW2) {
+      const int y = i / W2;
+      base = y * pg2.PADW + (i - y * W2);
+    }
+    tb[i] = base;
+  }
+  // halos, once: interiors are overwritten every sample
+  for (int i = threadIdx.x; i < COUT2 * pg2.cs; i += kBlock) dclds[i] = 0.0f;
+  for (int i = threadIdx.x; i < CIN1 * pg1.cs; i += kBlock) ilds[i] = 0.0f;
+  __syncthreads();
+  sc.store(dpooled2 + n * cells2, argmax2 + n * cells2, cells2, cell_vec, code_of, put);
+  __syncthreads();
+
+  // MFMA phase roles
+  const int lane = threadIdx.x & (kWave - 1);
+  const int quad = lane >> 4, mc = lane & 15; // mc: din channel of the lane
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int cnt = (tiles - wave + 3) >> 2; // tiles wave, wave + 4, ... below `tiles`
+  int koff[9];
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int k = 4 * s + quad, co = k / 9, tap = k - 9 * co;
+    koff[s] = co * pg2.cs + (2 - tap / 3) * pg2.PADW + (2 - tap % 3);
+  }
+  const float* wbl = wb + lane;
+  // din(y, x) of channel c lies where dconv(y, x) of channel c did
+  float* gl = dclds + mc * pg2.cs + pg2.PADW + 1;
+  // tile `wave + 4 * j`: four positions of channel mc (they may span two
+  // rows, so four stores)
+  auto emit = [&](int j, const f4& a) {
+    const int r0 = 16 * (wave + 4 * j) + 4 * quad;
+    if (r0 < HW2 && mc < C1) { // HW2 % 4 == 0: r0 + 3 < HW2 too
+      const i4 o = *(const i4*)(tb + r0);
+      gl[o.x] = a.x;
+      gl[o.y] = a.y;
+      gl[o.z] = a.z;
+      gl[o.w] = a.w;
+    }
+  };
+
+  // gather phase roles
+  const int pairs = C1 * CIN1;
+  const int nslices = max(1, kBlock / pairs);
+  const int pair = threadIdx.x % pairs;
+  const int slice = threadIdx.x / pairs;
+  const int co = pair / CIN1;
+  const int ci = pair % CIN1;
+  const bool active = threadIdx.x < pairs * nslices;
+  // top-left padded offset of the window of cell `slice`, and its step to
+  // cell + nslices: W2 cells per row, two padded rows and columns per cell
+  const int pyx0 = (slice / W2) << 16 | (slice % W2); // cell `slice`: (py, px) in one register
+  const int pxstep = nslices % W2;
+  const int offstep = 2 * (nslices / W2) * pg1.PADW + 2 * pxstep;
+  const int offwrap = 2 * pg1.PADW - 2 * W2;
+  // the same walk over din in dclds
+  const int goffstep = (nslices / W2) * pg2.PADW + pxstep;
+  const int goffwrap = pg2.PADW - W2;
+
+  float acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float accb = 0.0f;
+
+  while (true) {
+    // successor of sample n in this workgroup's sequence
+    bool more = true;
+    int64_t nn = n + 1;
+    if (nn >= nend) {
+      chunk += gridDim.x;
+      nn = (int64_t)chunk * samples;
+      nend = min((int64_t)N, nn + samples);
+      more = chunk < nchunks;
+    }
+
+    // ---- A: din of sample n over dconv(n)
+    const int z = opaque(0);
+    const float* xn = x + n * xplane + z;
+    const uint8_t* a1n = argmax1 + n * cells1 + z;
+    sx.load(xn, xpieces, x_vec);
+    sa.load(a1n, cells1, am1_mode);
+    {
+      // cnt <= kMergedHold: chains of three tiles, then the fourth
+      int base[kMfmaChains];
+      f4 a0[kMfmaChains], a1[kMfmaChains]; // of a1 only [0] is live
+      const int nc = min(kMfmaChains, cnt); // 0 for a wave past the last tile
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        base[i] = tb[min(wave + 4 * max(0, min(i, nc - 1)), tiles - 1) * 16 + mc];
+        a0[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+      if (nc > 0) mfma_tiles(nc, dclds, wbl, base, koff, COUT2 / 4, 4 * pg2.cs, a0);
+      a1[0] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (cnt > kMfmaChains) {
+        base[0] = tb[(wave + 4 * kMfmaChains) * 16 + mc];
+        mfma_chains<1>(dclds, wbl, base, koff, COUT2 / 4, 4 * pg2.cs, a1);
+      }
+      __syncthreads(); // every wave is done reading dconv(n)
+#pragma unroll
+      for (int i = 0; i < kMfmaChains; ++i) {
+        if (i < nc) emit(i, a0[i]);
+      }
+      if (cnt > kMfmaChains) emit(kMfmaChains, a1[0]);
+    }
+    sx.store(xn, ilds, xpieces, x_vec, H1, W1, pg1);
+    sa.store(a1n, alds, cells1, am1_mode);
+    __syncthreads();
+
+    // ---- B: gather of sample n
+    const float* dpn = dpooled2 + nn * cells2 + z;
+    const uint8_t* a2n = argmax2 + nn * cells2 + z;
+    if (more) sc.load(dpn, a2n, cells2, cell_vec);
+    if (active) {
+      const float* ip = ilds + ci * pg1.cs;
+      const float* gp = dclds + co * pg2.cs + pg2.PADW + 1;
+      const uint8_t* ap = alds + co * HW2;
+      const int pyx = opaque(pyx0), py0 = pyx >> 16;
+      int px = pyx & 0xffff;
+      int off = 2 * py0 * pg1.PADW + 2 * px, goff = py0 * pg2.PADW + px;
+      for (int cell = slice; cell < HW2; cell += nslices) {
+        // branchless, as in conv3x3_relu_pool_bwd_weight_kernel: a gated
+        // cell contributes g = +0.0f through an in-bounds window
+        const uint32_t a = ap[cell];
+        const float gv = gp[goff];
+        const float g = (a & kGateBit) ? 0.0f : gv;
+        if (ci == 0) accb += g;
+        const float* iw = ip + off + (int)((a >> 1) & 1u) * pg1.PADW + (int)(a & 1u);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            acc[ky * 3 + kx] = fmaf(g, iw[ky * pg1.PADW + kx], acc[ky * 3 + kx]);
+          }
+        }
+        px += pxstep;
+        off += offstep;
+        goff += goffstep;
+        if (px >= W2) {
+          px -= W2;
+          off += offwrap;
+          goff += goffwrap;
+        }
+      }
+    }
+    __syncthreads(); // din(n) read: dclds may be refilled
+    if (more) sc.store(dpn, a2n, cells2, cell_vec, code_of, put);
+    __syncthreads();
+    if (!more) break;
+    n = nn;
+  }
+
+  const int t = opaque((int)threadIdx.x), fpairs = opaque(pairs); // the gather's roles again
+  const int fpair = t % fpairs, fslice = t / fpairs;
+  bwdw_finish_row(acc, accb, redlds, part, pairs, nslices, fpair, fslice, fpair / CIN1,
+                  fpair % CIN1, C1, t < pairs * nslices);
+}
+
 // Sums the `rows` partial rows of `part` [rows][cols] column by column in a
 // fixed order and STORES the totals to dw (cols < ndw) / db (the rest; may
 // be null), which need not be initialised. Workgroup = kRedCols columns x
@@ -1214,6 +1559,18 @@ static bool mfma_eligible(int CIN, int COUT) {
   if (COUT != 16 || CIN % 4 != 0 || CIN > 16) return false;
   const char* env = std::getenv("DMLCLOUD_SMALLCNN_MFMA");
   return env == nullptr || atoi(env) != 0;
+}
+
+// Samples per chunk of the bwd_weight kernels: chunk so that the grid stays
+// ~>= 512 blocks while cutting partial rows
+// (DMLCLOUD_SMALLCNN_BWDW_CHUNK overrides for tuning experiments)
+static int bwdw_chunk_samples(int N) {
+  if (const char* env = std::getenv("DMLCLOUD_SMALLCNN_BWDW_CHUNK")) {
+    return std::max(1, atoi(env));
+  }
+  int samples = 1;
+  while (samples < 16 && (N + samples * 2 - 1) / (samples * 2) >= 512) samples *= 2;
+  return samples;
 }
 
 void conv3x3_relu_pool_fwd(at::Tensor in, at::Tensor w, at::Tensor b, at::Tensor out,
@@ -1321,14 +1678,7 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
                   dw.numel() == (int64_t)COUT * CIN * 9,
               "dw must be contiguous fp32 [COUT,CIN,3,3]");
   TORCH_CHECK(!db.defined() || (db.is_contiguous() && db.numel() == COUT), "db must be [COUT]");
-  // chunk so that the grid stays ~>= 512 blocks while cutting partial rows
-  // (DMLCLOUD_SMALLCNN_BWDW_CHUNK overrides for tuning experiments)
-  int samples = 1;
-  if (const char* env = std::getenv("DMLCLOUD_SMALLCNN_BWDW_CHUNK")) {
-    samples = std::max(1, atoi(env));
-  } else {
-    while (samples < 16 && (N + samples * 2 - 1) / (samples * 2) >= 512) samples *= 2;
-  }
+  const int samples = bwdw_chunk_samples(N);
   if (N == 0) { // nothing to sum: the gradient of an empty batch is zero
     dw.zero_();
     if (db.defined()) db.zero_();
@@ -1384,6 +1734,96 @@ void conv3x3_relu_pool_bwd_weight(at::Tensor dpooled, at::Tensor argmax, at::Ten
   hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((cols + kRedCols - 1) / kRedCols),
                      dim3(kBlock), 0, stream, part.data_ptr<float>(), dw.data_ptr<float>(),
                      db.defined() ? db.data_ptr<float>() : nullptr, blocks, cols, ndw);
+}
+
+// Layer 2's bwd_data and layer 1's bwd_weight of the two-layer stack
+//   x [N,CIN1,H1,W1] -> layer 1 (C1 channels) -> layer 2 (16 channels),
+// for a layer 1 that needs no input gradient: dw1/db1 from layer 2's pool
+// gradient. Eligible shapes run conv3x3_relu_pool_bwd_data_weight_kernel;
+// the others, and every shape with DMLCLOUD_SMALLCNN_MERGE_BWD=0 (read per
+// call), run the two launchers above on a temporary din. Both give the same
+// bits.
+void conv3x3_relu_pool_bwd_data_weight(at::Tensor dpooled2, at::Tensor argmax2, at::Tensor w2,
+                                       at::Tensor argmax1, at::Tensor x, at::Tensor dw1,
+                                       at::Tensor db1) {
+  auto dev_ok = [&](const at::Tensor& t, at::ScalarType st) {
+    return t.defined() && t.is_cuda() && t.device() == x.device() && t.scalar_type() == st &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(x.defined() && x.is_cuda() && x.dim() == 4, "x must be a 4-d device tensor");
+  TORCH_CHECK(dev_ok(x, at::kFloat), "x must be contiguous fp32 on device");
+  TORCH_CHECK(dev_ok(dpooled2, at::kFloat), "dpooled2 must be contiguous fp32 on x's device");
+  TORCH_CHECK(dev_ok(w2, at::kFloat), "w2 must be contiguous fp32 on x's device");
+  TORCH_CHECK(dev_ok(dw1, at::kFloat), "dw1 must be contiguous fp32 on x's device");
+  TORCH_CHECK(dev_ok(db1, at::kFloat), "db1 must be contiguous fp32 on x's device");
+  TORCH_CHECK(dev_ok(argmax1, at::kByte), "argmax1 must be contiguous uint8 on x's device");
+  TORCH_CHECK(dev_ok(argmax2, at::kByte), "argmax2 must be contiguous uint8 on x's device");
+  const int64_t N = x.size(0), CIN1 = x.size(1), H1 = x.size(2), W1 = x.size(3);
+  TORCH_CHECK(dw1.dim() == 4 && dw1.size(1) == CIN1 && dw1.size(2) == 3 && dw1.size(3) == 3,
+              "dw1 must be [C1,CIN1,3,3]");
+  const int64_t C1 = dw1.size(0);
+  TORCH_CHECK(w2.dim() == 4 && w2.size(1) == C1 && w2.size(2) == 3 && w2.size(3) == 3,
+              "w2 must be [C2,C1,3,3]");
+  const int64_t C2 = w2.size(0);
+  // both layers pool 2x2
+  TORCH_CHECK(H1 > 0 && W1 > 0 && H1 % 4 == 0 && W1 % 4 == 0,
+              "H1 and W1 must be multiples of 4 for two 2x2 poolings");
+  const int64_t H2 = H1 / 2, W2 = W1 / 2;
+  TORCH_CHECK(db1.numel() == C1, "db1 must be [C1]");
+  TORCH_CHECK(argmax1.sizes() == at::IntArrayRef({N, C1, H2, W2}),
+              "argmax1 must be [N,C1,H1/2,W1/2]");
+  TORCH_CHECK(dpooled2.sizes() == at::IntArrayRef({N, C2, H2 / 2, W2 / 2}),
+              "dpooled2 must be [N,C2,H1/4,W1/4]");
+  TORCH_CHECK(argmax2.sizes() == dpooled2.sizes(), "argmax2 must be shaped like dpooled2");
+  TORCH_CHECK(C1 * CIN1 <= kBlock, "bwd_weight supports COUT*CIN <= ", kBlock);
+
+  const PlaneGeom pg1 = plane_geom(H1, W1), pg2 = plane_geom(H2, W2);
+  const int64_t HW2 = H2 * W2;
+  const int64_t tiles = (HW2 + 15) / 16;
+  const int64_t cells1 = C1 * HW2;
+  const int64_t lds_bytes =
+      (16 * pg2.cs + 16 * 9 * 16 + tiles * 16 + CIN1 * pg1.cs) * (int64_t)sizeof(float) +
+      ((cells1 + 15) & ~(int64_t)15);
+  const char* env = std::getenv("DMLCLOUD_SMALLCNN_MERGE_BWD");
+  const bool merged = (env == nullptr || atoi(env) != 0) && mfma_eligible(C1, C2) &&
+                      tiles <= 4 * kMergedHold && lds_bytes <= kMaxLds;
+  if (!merged) {
+    at::Tensor din = at::empty({N, C1, H2, W2}, x.options());
+    conv3x3_relu_pool_bwd_data(dpooled2, argmax2, w2, din);
+    conv3x3_relu_pool_bwd_weight(din, argmax1, x, dw1, db1);
+    return;
+  }
+  if (N == 0) { // nothing to sum: the gradient of an empty batch is zero
+    dw1.zero_();
+    db1.zero_();
+    return;
+  }
+  const int samples = bwdw_chunk_samples(N);
+  const int blocks = std::min(((int)N + samples - 1) / samples, kMaxGrid);
+  const int ndw = C1 * CIN1 * 9;
+  const int cols = ndw + C1;
+  at::Tensor part = at::empty({blocks, cols}, dw1.options());
+  auto stream = c10::hip::getCurrentHIPStream();
+  const int cells2 = 16 * (H2 / 2) * (W2 / 2);
+  const int x_vec = aligned_to(x.data_ptr(), 16);
+  const int cell_vec = cells_vectorizable(dpooled2, argmax2, cells2);
+  const int am1_mode = (cells1 % 16 == 0 && aligned_to(argmax1.data_ptr(), 16)) ? 2
+                       : aligned_to(argmax1.data_ptr(), 4)                       ? 1
+                                                                                 : 0;
+  const bool deep = stage_depth(CIN1 * H1 * W1 / 4) > 1;
+  auto kernel = (x_vec && cell_vec && am1_mode == 2)
+                    ? (deep ? conv3x3_relu_pool_bwd_data_weight_kernel<4, true>
+                            : conv3x3_relu_pool_bwd_data_weight_kernel<1, true>)
+                    : (deep ? conv3x3_relu_pool_bwd_data_weight_kernel<4, false>
+                            : conv3x3_relu_pool_bwd_data_weight_kernel<1, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), (int)lds_bytes, stream,
+                     dpooled2.data_ptr<float>(), argmax2.data_ptr<uint8_t>(),
+                     w2.data_ptr<float>(), argmax1.data_ptr<uint8_t>(), x.data_ptr<float>(),
+                     part.data_ptr<float>(), (int)N, (int)CIN1, (int)C1, (int)H1, (int)W1,
+                     samples, x_vec, cell_vec, am1_mode);
+  hipLaunchKernelGGL(bwd_weight_reduce_kernel, dim3((cols + kRedCols - 1) / kRedCols),
+                     dim3(kBlock), 0, stream, part.data_ptr<float>(), dw1.data_ptr<float>(),
+                     db1.data_ptr<float>(), blocks, cols, ndw);
 }
 
 } // namespace dmlamd

@@ -43,6 +43,46 @@ class _ConvReluPoolFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _ConvStack2Fn(torch.autograd.Function):
+    """Two fused layers whose first needs no input gradient (the image layer).
+
+    Forward is the two layers' forward kernels. Backward is layer 2's
+    bwd_weight and then ONE call for layer 2's bwd_data and layer 1's
+    bwd_weight: the gradient between the layers never goes to memory
+    (conv3x3_relu_pool_bwd_data_weight in ops/csrc/smallcnn.hip, which runs
+    the two separate kernels on a temporary for shapes it has no merged
+    kernel for). Bit for bit the layer-by-layer path.
+    """
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        N, _, H, W = x.shape
+        C1, C2 = w1.shape[0], w2.shape[0]
+
+        def empty(c, h, w, dtype):
+            return torch.empty(N, c, h, w, device=x.device, dtype=dtype)
+
+        pooled1, argmax1 = empty(C1, H // 2, W // 2, x.dtype), empty(C1, H // 2, W // 2, torch.uint8)
+        _C.conv3x3_relu_pool_fwd(x, w1, b1, pooled1, argmax1)
+        pooled2, argmax2 = empty(C2, H // 4, W // 4, x.dtype), empty(C2, H // 4, W // 4, torch.uint8)
+        _C.conv3x3_relu_pool_fwd(pooled1, w2, b2, pooled2, argmax2)
+        ctx.save_for_backward(x, pooled1, argmax1, argmax2, w2)
+        ctx.w1_shape = w1.shape
+        return pooled2
+
+    @staticmethod
+    def backward(ctx, dpooled2):
+        x, pooled1, argmax1, argmax2, w2 = ctx.saved_tensors
+        dpooled2 = dpooled2.contiguous()
+        dw2 = torch.empty_like(w2)
+        db2 = torch.empty(w2.shape[0], device=w2.device, dtype=w2.dtype)
+        _C.conv3x3_relu_pool_bwd_weight(dpooled2, argmax2, pooled1, dw2, db2)
+        dw1 = torch.empty(ctx.w1_shape, device=w2.device, dtype=w2.dtype)
+        db1 = torch.empty(ctx.w1_shape[0], device=w2.device, dtype=w2.dtype)
+        _C.conv3x3_relu_pool_bwd_data_weight(dpooled2, argmax2, w2, argmax1, x, dw1, db1)
+        return None, dw1, db1, dw2, db2
+
+
 class ConvReluPool2d(nn.Module):
     """conv3x3(pad=1) + ReLU + maxpool2x2, fused on gfx950.
 
@@ -80,6 +120,11 @@ class FusedMnistCNN(nn.Module):
         self.fc = nn.Linear(784, 10)
 
     def forward(self, x):
-        x = self.layer1(x)
-        x = self.layer2(x)
+        if x.is_cuda and is_available() and not x.requires_grad:
+            # one autograd node over both conv layers: see _ConvStack2Fn
+            l1, l2 = self.layer1, self.layer2
+            x = _ConvStack2Fn.apply(x, l1.weight, l1.bias, l2.weight, l2.bias)
+        else:
+            x = self.layer1(x)
+            x = self.layer2(x)
         return self.fc(x.flatten(1))

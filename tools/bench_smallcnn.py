@@ -4,7 +4,10 @@ Run on a GPU box:  python tools/bench_smallcnn.py [--no-torch] [batch ...]
 Prints per-kernel times (cuda events, 100 reps) for the two MNIST-CNN
 layer shapes, plus the torch/MIOpen equivalents for comparison (left out
 with --no-torch). Shapes that take the f32 MFMA path get a second row with
-DMLCLOUD_SMALLCNN_MFMA=0, the VALU kernels.
+DMLCLOUD_SMALLCNN_MFMA=0, the VALU kernels. The last row per batch is the
+two-layer stack's backward between the layers: conv2 bwd_data plus conv1
+bwd_weight as two calls, as the one merged call, and as that call with
+DMLCLOUD_SMALLCNN_MERGE_BWD=0.
 """
 
 import os
@@ -83,6 +86,43 @@ def bench_shape(n, cin, cout, hw, with_torch=True, mfma=True):
     print(f'{line} | torch fwd {t_tfwd:8.1f}us fwd+bwd {t_tfb:8.1f}us')
 
 
+def bench_stack(n, cin1=1, c1=16, hw=28, c2=16):
+    """conv2 bwd_data + conv1 bwd_weight on the stacked shapes: two calls
+    against conv3x3_relu_pool_bwd_data_weight on the same tensors."""
+    torch.manual_seed(0)
+    x = torch.randn(n, cin1, hw, hw, device=DEV)
+    w1 = torch.randn(c1, cin1, 3, 3, device=DEV) * 0.1
+    b1 = torch.randn(c1, device=DEV) * 0.1
+    w2 = torch.randn(c2, c1, 3, 3, device=DEV) * 0.1
+    b2 = torch.randn(c2, device=DEV) * 0.1
+    pooled1 = torch.empty(n, c1, hw // 2, hw // 2, device=DEV)
+    argmax1 = torch.empty_like(pooled1, dtype=torch.uint8)
+    _C.conv3x3_relu_pool_fwd(x, w1, b1, pooled1, argmax1)
+    pooled2 = torch.empty(n, c2, hw // 4, hw // 4, device=DEV)
+    argmax2 = torch.empty_like(pooled2, dtype=torch.uint8)
+    _C.conv3x3_relu_pool_fwd(pooled1, w2, b2, pooled2, argmax2)
+    dpooled2 = torch.randn_like(pooled2)
+    din = torch.empty_like(pooled1)
+    dw1, db1 = torch.empty_like(w1), torch.empty_like(b1)
+
+    def two_calls():
+        _C.conv3x3_relu_pool_bwd_data(dpooled2, argmax2, w2, din)
+        _C.conv3x3_relu_pool_bwd_weight(din, argmax1, x, dw1, db1)
+
+    def one_call():
+        _C.conv3x3_relu_pool_bwd_data_weight(dpooled2, argmax2, w2, argmax1, x, dw1, db1)
+
+    t_two = time_fn(two_calls)
+    t_one = time_fn(one_call)
+    os.environ['DMLCLOUD_SMALLCNN_MERGE_BWD'] = '0'  # read per call
+    t_off = time_fn(one_call)
+    os.environ.pop('DMLCLOUD_SMALLCNN_MERGE_BWD')
+    print(
+        f'N={n:6d} stack {cin1}->{c1}->{c2} hw={hw:2d} | bwd_data2 + bwd_w1 {t_two:8.1f}us '
+        f'merged {t_one:8.1f}us merged, switch 0 {t_off:8.1f}us'
+    )
+
+
 if __name__ == '__main__':
     args = sys.argv[1:]
     with_torch = '--no-torch' not in args
@@ -91,3 +131,4 @@ if __name__ == '__main__':
         bench_shape(n, 1, 16, 28, with_torch)  # conv1 shape
         bench_shape(n, 16, 16, 14, with_torch)  # conv2 shape
         bench_shape(n, 16, 16, 14, False, mfma=False)  # conv2 shape, VALU kernels
+        bench_stack(n)

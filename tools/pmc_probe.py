@@ -37,6 +37,17 @@ def main():
             _C.conv3x3_relu_pool_bwd_data(dpooled, argmax, w, din)
             _C.conv3x3_relu_pool_bwd_weight(dpooled, argmax, x, dw, db)
 
+    # the two-layer stack's merged backward (conv2 bwd_data + conv1 bwd_weight)
+    x = torch.randn(n, 1, 28, 28, device=DEV)
+    argmax1 = torch.randint(0, 8, (n, 16, 14, 14), device=DEV, dtype=torch.uint8)
+    argmax2 = torch.randint(0, 8, (n, 16, 7, 7), device=DEV, dtype=torch.uint8)
+    dpooled2 = torch.randn(n, 16, 7, 7, device=DEV)
+    w2 = torch.randn(16, 16, 3, 3, device=DEV) * 0.1
+    dw1 = torch.empty(16, 1, 3, 3, device=DEV)
+    db1 = torch.empty(16, device=DEV)
+    for _ in range(3):
+        _C.conv3x3_relu_pool_bwd_data_weight(dpooled2, argmax2, w2, argmax1, x, dw1, db1)
+
     if '--smallcnn-only' in args:
         torch.cuda.synchronize()
         print('pmc probe done')
