@@ -10,10 +10,17 @@ integer [B, T] tensor whose runs of equal values are the documents packed
 into each row. Attention then stays inside a document and the learned
 positions restart at every document start, so each document is computed
 exactly as if it were alone in its row.
+
+Grouped-query attention: `GPT2Config.n_kv_head` (a divisor of `n_head`)
+gives K and V fewer heads than Q. `c_attn` then projects to
+`n_embd + 2 * n_kv_head * head_dim` features and query head h reads K/V
+head h // (n_head // n_kv_head). `None` (or `n_head`) is plain GPT-2,
+unchanged.
 """
 
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 from torch import nn
@@ -32,6 +39,7 @@ class GPT2Config:
     n_layer: int = 12
     n_head: int = 12
     dropout: float = 0.0
+    n_kv_head: Optional[int] = None  # K/V heads (GQA); None = n_head
 
 
 class CausalSelfAttention(nn.Module):
@@ -39,16 +47,21 @@ class CausalSelfAttention(nn.Module):
         super().__init__()
         assert cfg.n_embd % cfg.n_head == 0
         self.n_head = cfg.n_head
-        self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
+        self.n_kv_head = cfg.n_head if cfg.n_kv_head is None else cfg.n_kv_head
+        assert self.n_kv_head >= 1 and cfg.n_head % self.n_kv_head == 0, 'n_kv_head must divide n_head'
+        self.kv_dim = self.n_kv_head * (cfg.n_embd // cfg.n_head)  # n_embd unless grouped
+        self.c_attn = nn.Linear(cfg.n_embd, cfg.n_embd + 2 * self.kv_dim)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
 
     def forward(self, x, doc_start=None):
         B, T, C = x.shape
         qkv = self.c_attn(x)
-        q, k, v = qkv.split(C, dim=2)
+        # strided views into qkv, handed to sdpa without a copy; with
+        # n_kv_head < n_head, k and v are [B, n_kv_head, T, hd]
+        q, k, v = qkv.split([C, self.kv_dim, self.kv_dim], dim=2)
         q = q.view(B, T, self.n_head, C // self.n_head).transpose(1, 2)
-        k = k.view(B, T, self.n_head, C // self.n_head).transpose(1, 2)
-        v = v.view(B, T, self.n_head, C // self.n_head).transpose(1, 2)
+        k = k.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
+        v = v.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
         # custom MFMA flash attention on bf16/D=64 (ops/fused_attn.py);
         # beats AOTriton fwd+bwd combined at this shape — falls back to
         # torch SDPA otherwise
@@ -124,10 +137,10 @@ class GPT2(nn.Module):
         return logits, loss
 
 
-def gpt2_small() -> GPT2:
-    return GPT2(GPT2Config())
+def gpt2_small(n_kv_head: Optional[int] = None) -> GPT2:
+    return GPT2(GPT2Config(n_kv_head=n_kv_head))
 
 
-def gpt2_tiny() -> GPT2:
+def gpt2_tiny(n_kv_head: Optional[int] = None) -> GPT2:
     """Small config for CPU tests."""
-    return GPT2(GPT2Config(vocab_size=512, n_positions=64, n_embd=64, n_layer=2, n_head=2))
+    return GPT2(GPT2Config(vocab_size=512, n_positions=64, n_embd=64, n_layer=2, n_head=2, n_kv_head=n_kv_head))

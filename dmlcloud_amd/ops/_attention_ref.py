@@ -261,6 +261,7 @@ def flash_attn_bwd_padded(
         return p, ds
 
     # ---- dK / dV: 64-key blocks of 4 waves x 16 keys, 32-row q steps ----
+    # (gqa_bwd_padded below emulates the <kGqa> form of this loop nest)
     nkb = (N + 63) // 64
     for kb0 in range(0, nkb * 64, 64):
         i_start = (kb0 & ~31) if causal else 0
@@ -328,3 +329,106 @@ def mha_fwd_tiled(q, k, v, causal=True, bq=32, bk=64):
         for h in range(H):
             o[b, h], lse[b, h] = flash_attn_fwd_tiled(q[b, h], k[b, h], v[b, h], causal, bq, bk)
     return o, lse
+
+
+# ---------------------------------------------------------------------------
+# Grouped-query attention: the kernels' <kGqa = true> instantiations
+# ---------------------------------------------------------------------------
+#
+# q is [B, H, N, D], k and v are [B, Hkv, N, D], G = H // Hkv, and query
+# head h reads K/V head h // G. Forward and dQ are the per-slice functions
+# above on another K/V slice. dK/dV is one block per (b, K/V head, 64-key
+# block) that walks the q-steps of the group's G heads one head after the
+# other, in ascending head order, into ONE accumulator per wave, and stores
+# each element once.
+
+
+def gqa_fwd_padded(q, k, v, causal=True, scale=None, doc_start=None):
+    """attn_fwd_kernel<..., kGqa = true>: (o [B, H, N, D], lse [B, H, N]).
+    `doc_start` is [B, N] or None."""
+    B, H, N, D = q.shape
+    Hkv = k.shape[1]
+    assert v.shape == k.shape and H % Hkv == 0
+    G = H // Hkv
+    o = torch.empty(B, H, N, D, dtype=torch.float32)
+    lse = torch.empty(B, H, N, dtype=torch.float32)
+    for b in range(B):
+        ds = None if doc_start is None else doc_start[b]
+        for h in range(H):
+            o[b, h], lse[b, h] = flash_attn_fwd_padded(q[b, h], k[b, h // G], v[b, h // G], causal, scale, ds)
+    return o, lse
+
+
+def gqa_bwd_padded(do, q, k, v, o, lse, causal=True, scale=None, doc_start=None):
+    """attn_bwd_delta_kernel + the <kGqa = true> dK/dV and dQ kernels:
+    (dq [B, H, N, D], dk [B, Hkv, N, D], dv [B, Hkv, N, D])."""
+    B, H, N, D = q.shape
+    Hkv = k.shape[1]
+    assert v.shape == k.shape and H % Hkv == 0
+    assert doc_start is None or causal, 'doc_start requires causal attention'
+    G = H // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    scale2 = scale * _LOG2E
+    qf, kf, vf, dof, of = (t.float() for t in (q, k, v, do, o))
+    lse2 = lse.float() * _LOG2E
+    delta = (dof * of).sum(dim=-1)  # [B, H, N]
+
+    dq = torch.empty(B, H, N, D)
+    dk = torch.full((B, Hkv, N, D), float('nan'))
+    dv = torch.full((B, Hkv, N, D), float('nan'))
+
+    # dQ: per (b, query head) exactly flash_attn_bwd_padded's, on the
+    # group's K/V slice
+    for b in range(B):
+        ds = None if doc_start is None else doc_start[b]
+        for h in range(H):
+            dq[b, h], _, _ = flash_attn_bwd_padded(
+                do[b, h], q[b, h], k[b, h // G], v[b, h // G], o[b, h], lse[b, h], causal, scale, ds
+            )
+
+    # dK / dV: one block per (b, K/V head, 64-key block)
+    nkb = (N + 63) // 64
+    for b in range(B):
+        ds = None if doc_start is None else doc_start[b]
+        for kvh in range(Hkv):
+            for kb0 in range(0, nkb * 64, 64):
+                i_start = (kb0 & ~31) if causal else 0
+                # the break depends on (b, kb0, i0) only: the same for every head
+                i_stop = N
+                if ds is not None:
+                    for i0 in range(i_start, N, 32):
+                        if _dstart1(ds, i0, N) > kb0 + 63:
+                            i_stop = i0
+                            break
+                for wave in range(4):
+                    j0 = kb0 + 16 * wave
+                    if not j0 < N:  # `valid`
+                        continue
+                    key_g = j0 + torch.arange(16)
+                    kr = _crow(key_g, N)
+                    krows, vrows = kf[b, kvh][kr], vf[b, kvh][kr]  # kf / vf2, loaded once
+                    dv_acc = torch.zeros(16, D)
+                    dk_acc = torch.zeros(16, D)
+                    for g in range(G):  # the group's heads, ascending
+                        h = kvh * G + g
+                        for i0 in range(i_start, i_stop, 32):
+                            if causal and not i0 + 32 > j0:
+                                continue
+                            for hq in range(2):
+                                q_g = i0 + 16 * hq + torch.arange(16)
+                                qr = _crow(q_g, N)
+                                s2 = (qf[b, h][qr] @ krows.T) * scale2
+                                dp = dof[b, h][qr] @ vrows.T
+                                live = (key_g < N).unsqueeze(0) & (q_g < N).unsqueeze(1)
+                                if causal:
+                                    live = live & (key_g.unsqueeze(0) <= q_g.unsqueeze(1))
+                                if ds is not None:
+                                    live = live & (key_g.unsqueeze(0) >= _dstart(ds, q_g, N).unsqueeze(1))
+                                p = torch.where(live, torch.exp2(s2 - lse2[b, h][qr].unsqueeze(1)), torch.zeros(()))
+                                dsc = p * (dp - delta[b, h][qr].unsqueeze(1)) * scale
+                                dv_acc += p.T @ dof[b, h][qr]
+                                dk_acc += dsc.T @ qf[b, h][qr]
+                    keep = key_g < N
+                    dv[b, kvh][key_g[keep]] = dv_acc[keep]
+                    dk[b, kvh][key_g[keep]] = dk_acc[keep]
+    return dq, dk, dv

@@ -157,6 +157,35 @@ struct StridesDoc : Strides {
 template <>
 struct StridesDoc<false> : Strides {};
 
+// Grouped-query attention (GQA; MQA is Hkv = 1): every kernel below also
+// takes a `kGqa` template flag. K and V (and dK, dV) then have Hkv = H / G
+// heads, G an integer >= 1, and query head h reads K/V head h / G: the
+// layout of repeat_interleave(G, dim=1), not h % Hkv. BH and H keep
+// counting QUERY heads in every kernel. <kGqa = false> is the code without
+// it, unchanged. <true>:
+//   * forward and dQ keep their block per (b, query head, row block) and
+//     every loop; only kp/vp come from kv_slice(): head (bh % H) / G;
+//   * dK/dV runs one block per (b, K/V head, 64-key block) and walks the
+//     q-steps of the group's G query heads one head after the other into
+//     the same accumulators (the argument stands next to that loop).
+// G rides in the K stride argument, a StridesGqa<kGqa>, for the reason
+// doc_start rides in a StridesDoc: the <false> argument layout stays.
+template <bool kGqa>
+struct StridesGqa : Strides {
+  int group; // G = H / Hkv
+};
+template <>
+struct StridesGqa<false> : Strides {};
+
+// The (b, K/V head) slice of k or v that query-head index bh reads.
+template <bool kGqa>
+__device__ __forceinline__ const __hip_bfloat16* kv_slice(const __hip_bfloat16* t,
+                                                          const Strides& st, int bh, int H,
+                                                          const StridesGqa<kGqa>& sk) {
+  if constexpr (kGqa) return t + (int64_t)(bh / H) * st.b + (int64_t)((bh % H) / sk.group) * st.h;
+  else return tslice(t, st, bh, H);
+}
+
 // The row is clamped to N - 1 in every instantiation: an aligned N still
 // has 128-row forward blocks whose last waves lie wholly past N.
 __device__ __forceinline__ int dstart(const int* __restrict__ ds, int row, int N) {
@@ -194,12 +223,12 @@ __device__ __forceinline__ float bwd_prob(float s, float scale, float lse2, int 
 // waves/SIMD via amdgpu_waves_per_eu(3) spills 164 B/lane and measured
 // SLOWER (552 vs 508 us causal at the GPT-2 shape) — the spill traffic
 // in the inner loop outweighs the extra latency hiding. Keep 2 waves.
-template <bool kRagged, bool kDoc>
+template <bool kRagged, bool kDoc, bool kGqa>
 __global__ void __launch_bounds__(kAttnThreads) attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ o,
     float* __restrict__ lse, int BH, int H, int N, float scale, bool causal_arg, Strides sq,
-    Strides sk, StridesDoc<kDoc> sv) {
+    StridesGqa<kGqa> sk, StridesDoc<kDoc> sv) {
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStrideF];
   __shared__ __hip_bfloat16 k_lds[2][kKTF][kKVStride];
@@ -226,8 +255,8 @@ __global__ void __launch_bounds__(kAttnThreads) attn_fwd_kernel(
     const int i0 = qb0 + wave * 2 * kQT; // this wave's 32 q rows
     const bool valid = i0 < N;
     const __hip_bfloat16* qp = tslice(q, sq, bh, H);
-    const __hip_bfloat16* kp = tslice(k, sk, bh, H);
-    const __hip_bfloat16* vp = tslice(v, sv, bh, H);
+    const __hip_bfloat16* kp = kv_slice(k, sk, bh, H, sk);
+    const __hip_bfloat16* vp = kv_slice(v, sv, bh, H, sk);
 
     bf16x8 qf[2][2]; // [sub-tile][k-chunk]
     if (valid) {
@@ -479,14 +508,27 @@ static StridesDoc<kDoc> doc_strides_of(const at::Tensor& t, const int* doc_start
   else return {strides_of(t)};
 }
 
-// f(bool_constant<kRagged>, bool_constant<kDoc>): an aligned N keeps the
-// unmasked code, any other the clamped/masked/predicated one; a doc_start kDoc.
+// The kernels' K stride argument (see StridesGqa).
+template <bool kGqa>
+static StridesGqa<kGqa> gqa_strides_of(const at::Tensor& t, int group) {
+  if constexpr (kGqa) return {strides_of(t), group};
+  else return {strides_of(t)};
+}
+
+// f(bool_constant<kRagged>, bool_constant<kDoc>, bool_constant<kGqa>): an
+// aligned N keeps the unmasked code, any other the clamped/masked/predicated
+// one; a doc_start kDoc; fewer K/V heads than query heads kGqa.
 template <typename F>
-static void with_variant(bool ragged, bool has_doc, F&& f) {
+static void with_variant(bool ragged, bool has_doc, bool gqa, F&& f) {
+  auto pick_gqa = [&](auto ragged_c, auto doc_c) {
+    gqa ? f(ragged_c, doc_c, std::true_type{}) : f(ragged_c, doc_c, std::false_type{});
+  };
   if (ragged) {
-    has_doc ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    has_doc ? pick_gqa(std::true_type{}, std::true_type{})
+            : pick_gqa(std::true_type{}, std::false_type{});
   } else {
-    has_doc ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+    has_doc ? pick_gqa(std::false_type{}, std::true_type{})
+            : pick_gqa(std::false_type{}, std::false_type{});
   }
 }
 
@@ -496,30 +538,48 @@ static int attn_grid(int BH, int N, int rows_per_block) {
 }
 
 // Everything both launchers require of their tensors, before any launch.
-// `strided`: bf16 on q's device, shaped like q, last dim contiguous (reached
-// through per-tensor strides). `dense`: the same, but indexed as contiguous
-// [BH, N, 64]. `row_stats` (lse, delta): fp32 on q's device, >= B*H*N elements.
+// q is [B, H, N, 64]; k is [B, Hkv, N, 64] with 1 <= Hkv <= H and H % Hkv == 0
+// (Hkv < H is grouped-query attention). `strided`: bf16 on q's device, last
+// dim contiguous (reached through per-tensor strides), `like_q` shaped like q
+// and `like_k` shaped like k. `dense`: the same, but indexed as contiguous
+// [B*heads, N, 64]. `row_stats` (lse, delta): fp32 on q's device, >= B*H*N
+// elements. Returns the group size G = H / Hkv.
 using NamedTensor = std::pair<const char*, const at::Tensor&>;
-static void check_attn_args(const at::Tensor& q, std::initializer_list<NamedTensor> strided,
-                            std::initializer_list<NamedTensor> dense,
-                            std::initializer_list<NamedTensor> row_stats) {
+using NamedTensors = std::initializer_list<NamedTensor>;
+static int check_attn_args(const at::Tensor& q, const at::Tensor& k, NamedTensors strided_like_q,
+                           NamedTensors strided_like_k, NamedTensors dense_like_q,
+                           NamedTensors dense_like_k, NamedTensors row_stats) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1,
               "q must be a device tensor [B,H,N,64] with N >= 1 (head dim 64 only)");
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == q.size(0) && k.size(2) == q.size(2) &&
+                  k.size(3) == kAttnD && k.size(1) >= 1 && k.size(1) <= q.size(1) &&
+                  q.size(1) % k.size(1) == 0,
+              "k must be [B,Hkv,N,64] with q's B and N (self-attention geometry) and a head "
+              "count Hkv that divides q's: got ", k.sizes(), " for q ", q.sizes());
   auto check = [&](const NamedTensor& a, at::ScalarType dtype, bool layout, const char* want) {
     TORCH_CHECK(a.second.scalar_type() == dtype && a.second.device() == q.device() && layout,
                 a.first, " must be ", want, " on q's device");
   };
-  for (const NamedTensor& a : strided) {
+  for (const NamedTensor& a : strided_like_q) {
     check(a, at::kBFloat16, a.second.sizes() == q.sizes() && a.second.stride(3) == 1,
-          "bf16, shaped like q (self-attention geometry), last dim contiguous,");
+          "bf16, shaped like q, last dim contiguous,");
   }
-  for (const NamedTensor& a : dense) {
+  for (const NamedTensor& a : strided_like_k) {
+    check(a, at::kBFloat16, a.second.sizes() == k.sizes() && a.second.stride(3) == 1,
+          "bf16, shaped like k ([B,Hkv,N,64]), last dim contiguous,");
+  }
+  for (const NamedTensor& a : dense_like_q) {
     check(a, at::kBFloat16, a.second.sizes() == q.sizes() && a.second.is_contiguous(),
           "bf16, shaped like q, contiguous,");
+  }
+  for (const NamedTensor& a : dense_like_k) {
+    check(a, at::kBFloat16, a.second.sizes() == k.sizes() && a.second.is_contiguous(),
+          "bf16, shaped like k ([B,Hkv,N,64]), contiguous,");
   }
   for (const NamedTensor& a : row_stats) {
     check(a, at::kFloat, a.second.numel() >= q.size(0) * q.size(1) * q.size(2), "fp32[B*H*N]");
   }
+  return (int)(q.size(1) / k.size(1));
 }
 
 // doc_start, when given: int32 [B, N], contiguous, on q's device, causal
@@ -539,19 +599,20 @@ static const int* checked_doc_start(const c10::optional<at::Tensor>& doc_start,
 
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
               double scale, bool causal, c10::optional<at::Tensor> doc_start) {
-  check_attn_args(q, {{"q", q}, {"k", k}, {"v", v}}, {{"o", o}}, {{"lse", lse}});
+  const int G = check_attn_args(q, k, {{"q", q}}, {{"k", k}, {"v", v}}, {{"o", o}}, {},
+                                {{"lse", lse}});
   const int* dsp = checked_doc_start(doc_start, q, causal);
   const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
   auto stream = c10::hip::getCurrentHIPStream();
   static_assert(kKTF % (2 * kQT) == 0); // a wave's 32 q rows also end at N then
-  with_variant(N % kKTF != 0, dsp != nullptr, [&](auto ragged, auto doc) {
-    constexpr bool kDoc = decltype(doc)::value;
-    hipLaunchKernelGGL((attn_fwd_kernel<decltype(ragged)::value, kDoc>),
+  with_variant(N % kKTF != 0, dsp != nullptr, G > 1, [&](auto ragged, auto doc, auto gqa) {
+    constexpr bool kDoc = decltype(doc)::value, kGqa = decltype(gqa)::value;
+    hipLaunchKernelGGL((attn_fwd_kernel<decltype(ragged)::value, kDoc, kGqa>),
                        dim3(attn_grid(BH, N, kFwdRowsPerBlock)), dim3(kAttnThreads), 0, stream,
                        (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
                        (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)o.data_ptr(),
                        lse.data_ptr<float>(), BH, H, N, (float)scale, causal, strides_of(q),
-                       strides_of(k), doc_strides_of<kDoc>(v, dsp));
+                       gqa_strides_of<kGqa>(k, G), doc_strides_of<kDoc>(v, dsp));
   });
 }
 
@@ -601,13 +662,14 @@ __global__ void __launch_bounds__(kBlock) attn_bwd_delta_kernel(
 // Block = 4 waves, each owning a 16-key tile of one (b,h); q-tiles of 32
 // rows (Q and dO staged in shared LDS) stream past. Per q-tile, per wave:
 // 2 MFMAs S^T, 2 MFMAs dP^T, 4+4 MFMAs dV/dK accumulation (k = 32 q rows).
-template <bool kRagged, bool kDoc>
+template <bool kRagged, bool kDoc, bool kGqa>
 __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dk, __hip_bfloat16* __restrict__ dv, int BH, int H, int N,
-    float scale, bool causal_arg, Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
+    float scale, bool causal_arg, Strides sq, StridesGqa<kGqa> sk, Strides sv,
+    StridesDoc<kDoc> sdo) {
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   constexpr int kQStep = 32; // q rows per iteration (MFMA contraction width)
   static_assert(kQStep * kAttnD == kImgElems);
@@ -622,19 +684,26 @@ __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dkdv_kernel(
   __hip_bfloat16(*dst_lds)[kPStride] = dst_lds_all[wave];
 
   const int nkb = (N + kBwdKeysPerBlock - 1) / kBwdKeysPerBlock;
-  const int64_t total_blocks = (int64_t)BH * nkb;
+  // kGqa: a block belongs to one (b, K/V head) and `bh` below counts those,
+  // B * Hkv = BH / G of them; bh * group is then the (b, query head) index
+  // of the first head of its group (kv_slice maps it back to the K/V
+  // head), and the group's heads follow it.
+  int group = 1;
+  if constexpr (kGqa) group = sk.group;
+  const int64_t total_blocks = (int64_t)(BH / group) * nkb;
 
   for (int64_t blk = blockIdx.x; blk < total_blocks; blk += gridDim.x) {
     const int bh = blk / nkb;
     const int kb0 = (blk - (int64_t)bh * nkb) * kBwdKeysPerBlock;
     const int j0 = kb0 + wave * 16; // this wave's 16 keys
     const bool valid = j0 < N;
-    const __hip_bfloat16* qp = tslice(q, sq, bh, H);
-    const __hip_bfloat16* kp = tslice(k, sk, bh, H);
-    const __hip_bfloat16* vp = tslice(v, sv, bh, H);
-    const __hip_bfloat16* dop = tslice(dout, sdo, bh, H);
-    const float* lsep = lse + (int64_t)bh * N;
-    const float* delp = delta + (int64_t)bh * N;
+    // q-side pointers of the group's first head (of THE head without kGqa)
+    const __hip_bfloat16* qp = tslice(q, sq, bh * group, H);
+    const __hip_bfloat16* kp = kv_slice(k, sk, bh * group, H, sk);
+    const __hip_bfloat16* vp = kv_slice(v, sv, bh * group, H, sk);
+    const __hip_bfloat16* dop = tslice(dout, sdo, bh * group, H);
+    const float* lsep = lse + (int64_t)bh * group * N;
+    const float* delp = delta + (int64_t)bh * group * N;
 
     // wave-local K and V fragments for this key tile (row-major loads)
     bf16x8 kf[2], vf2[2];
@@ -672,80 +741,108 @@ __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dkdv_kernel(
     // the loop. The test depends on (bh, kb0, i0) only, so the break is
     // block-uniform and sits before the step's barriers. A malformed
     // doc_start can only end the loop early (fewer terms, never a fault).
+    // Groups (kGqa): dK[key] = sum over the group's G query heads of that
+    // head's dS^T Q, and dV likewise, so the q-step walk above runs once
+    // per head, in ascending head order, with that head's qp / dop / lsep /
+    // delp, and every pass adds into the SAME dv_acc / dk_acc: the group
+    // sum happens in the fp32 accumulators and each output element is
+    // rounded and stored once. kf / vf2 are loaded once (all G heads read
+    // this K/V head). Nothing above depends on the head: i_start, the
+    // per-wave skip and valid are functions of (kb0, j0, i0), and doc_start
+    // is shared by all heads, so under kDoc the break ends ONE head's walk
+    // after the same number of steps for each head; the next head starts
+    // again at i_start with step_start reloaded. The test still depends on
+    // (b, kb0, i0) only, so it stays block-uniform for every head. Every
+    // step ends with a barrier, so a head's first staging never overtakes
+    // a reader of the previous head's last tiles. Query head g of the group
+    // is (b, query head) index bh * group + g. <kGqa = false>: the do-while
+    // is the code it wraps, run once.
     const int* dsp = nullptr;
-    if constexpr (kDoc) dsp = sdo.doc_start + (int64_t)(bh / H) * N;
+    if constexpr (kDoc) dsp = sdo.doc_start + (int64_t)(bh * group / H) * N;
     const int i_start = causal ? (kb0 & ~(kQStep - 1)) : 0; // block-aligned diag
-    // (the start of the NEXT step's first row is loaded a step ahead, so
-    // the test does not wait on memory in front of the barrier)
-    int step_start = 0;
-    if constexpr (kDoc) step_start = dstart(dsp, i_start, N);
-    for (int i0 = i_start; i0 < N; i0 += kQStep) {
-      if constexpr (kDoc) {
-        if (step_start > kb0 + kBwdKeysPerBlock - 1) break;
-        step_start = dstart(dsp, i0 + kQStep, N);
-      }
-      // ---- stage Q and dO into tiled images (one bf16x8 per thread) ----
-      const int st_t = vt_idx(st_row, st_col);
-      const int st_g = crow<kRagged>(i0 + st_row, N);
-      *(bf16x8*)(&q_lds[st_t]) = *(const bf16x8*)(qp + (int64_t)st_g * sq.r + st_col);
-      *(bf16x8*)(&do_lds[st_t]) = *(const bf16x8*)(dop + (int64_t)st_g * sdo.r + st_col);
-      __syncthreads();
+    int g = 0;
+    do {
+      // (the start of the NEXT step's first row is loaded a step ahead, so
+      // the test does not wait on memory in front of the barrier)
+      int step_start = 0;
+      if constexpr (kDoc) step_start = dstart(dsp, i_start, N);
+      for (int i0 = i_start; i0 < N; i0 += kQStep) {
+        if constexpr (kDoc) {
+          if (step_start > kb0 + kBwdKeysPerBlock - 1) break;
+          step_start = dstart(dsp, i0 + kQStep, N);
+        }
+        // ---- stage Q and dO into tiled images (one bf16x8 per thread) ----
+        const int st_t = vt_idx(st_row, st_col);
+        const int st_g = crow<kRagged>(i0 + st_row, N);
+        *(bf16x8*)(&q_lds[st_t]) = *(const bf16x8*)(qp + (int64_t)st_g * sq.r + st_col);
+        *(bf16x8*)(&do_lds[st_t]) = *(const bf16x8*)(dop + (int64_t)st_g * sdo.r + st_col);
+        __syncthreads();
 
-      if (valid && (!causal || i0 + kQStep > j0)) {
-        // two 16-q halves share this wave's key tile
+        if (valid && (!causal || i0 + kQStep > j0)) {
+          // two 16-q halves share this wave's key tile
 #pragma unroll
-        for (int hq = 0; hq < 2; ++hq) {
-          const int q0 = i0 + 16 * hq; // this half's first q row
-          const int qr = crow<kRagged>(q0 + row16, N);
-          const float lse2_q = lsep[qr] * kLog2e; // log2 domain
-          const float del_q = delp[qr];
-          // kDoc: row q reads keys q_lo <= key <= q_hi = q (causal); a
-          // padded row q >= N gets the empty range (q_hi = -1 < q_lo)
-          int q_lo = 0, q_hi = 0;
-          if constexpr (kDoc) {
-            q_lo = dstart(dsp, q0 + row16, N);
-            q_hi = (!kRagged || q0 + row16 < N) ? q0 + row16 : -1;
+          for (int hq = 0; hq < 2; ++hq) {
+            const int q0 = i0 + 16 * hq; // this half's first q row
+            const int qr = crow<kRagged>(q0 + row16, N);
+            const float lse2_q = lsep[qr] * kLog2e; // log2 domain
+            const float del_q = delp[qr];
+            // kDoc: row q reads keys q_lo <= key <= q_hi = q (causal); a
+            // padded row q >= N gets the empty range (q_hi = -1 < q_lo)
+            int q_lo = 0, q_hi = 0;
+            if constexpr (kDoc) {
+              q_lo = dstart(dsp, q0 + row16, N);
+              q_hi = (!kRagged || q0 + row16 < N) ? q0 + row16 : -1;
+            }
+
+            // ---- S^T = K Q^T (rows = key, cols = q) ----
+            f32x4 acc = {0, 0, 0, 0};
+            f32x4 dpt = {0, 0, 0, 0};
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              const int rm = vt_idx(16 * hq + row16, 32 * c + 8 * grp);
+              const bf16x8 qfr = *(const bf16x8*)(&q_lds[rm]);
+              const bf16x8 dof = *(const bf16x8*)(&do_lds[rm]);
+              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[c], qfr, acc, 0, 0, 0);
+              dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf2[c], dof, dpt, 0, 0, 0);
+            }
+
+            // ---- P^T and dS^T in C layout; write transposed slices ----
+            // lane holds keys 4grp+r (rows), q = row16 (col)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float p = bwd_prob<kRagged, kDoc>(acc[r], scale, lse2_q, j0 + 4 * grp + r,
+                                                      q0 + row16, q_lo, q_hi, causal, N);
+              const float ds = p * (dpt[r] - del_q) * scale;
+              // [key][q] slices: q column of this half = 16*hq + row16
+              pt_lds[4 * grp + r][16 * hq + row16] = __float2bfloat16(p);
+              dst_lds[4 * grp + r][16 * hq + row16] = __float2bfloat16(ds);
+            }
           }
+          // same-wave LDS visibility; A-operand reads below
 
-          // ---- S^T = K Q^T (rows = key, cols = q) ----
-          f32x4 acc = {0, 0, 0, 0};
-          f32x4 dpt = {0, 0, 0, 0};
+          // ---- dV += P^T @ dO ; dK += dS^T @ Q  (contraction over 32 q) ----
+          const bf16x8 ptf = *(const bf16x8*)(&pt_lds[row16][8 * grp]);
+          const bf16x8 dstf = *(const bf16x8*)(&dst_lds[row16][8 * grp]);
 #pragma unroll
-          for (int c = 0; c < 2; ++c) {
-            const int rm = vt_idx(16 * hq + row16, 32 * c + 8 * grp);
-            const bf16x8 qfr = *(const bf16x8*)(&q_lds[rm]);
-            const bf16x8 dof = *(const bf16x8*)(&do_lds[rm]);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[c], qfr, acc, 0, 0, 0);
-            dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf2[c], dof, dpt, 0, 0, 0);
-          }
-
-          // ---- P^T and dS^T in C layout; write transposed slices ----
-          // lane holds keys 4grp+r (rows), q = row16 (col)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float p = bwd_prob<kRagged, kDoc>(acc[r], scale, lse2_q, j0 + 4 * grp + r,
-                                                    q0 + row16, q_lo, q_hi, causal, N);
-            const float ds = p * (dpt[r] - del_q) * scale;
-            // [key][q] slices: q column of this half = 16*hq + row16
-            pt_lds[4 * grp + r][16 * hq + row16] = __float2bfloat16(p);
-            dst_lds[4 * grp + r][16 * hq + row16] = __float2bfloat16(ds);
+          for (int db = 0; db < 4; ++db) {
+            const bf16x8 dob = read_tr_frag(do_lds, db, lane);
+            const bf16x8 qb = read_tr_frag(q_lds, db, lane);
+            dv_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf, dob, dv_acc[db], 0, 0, 0);
+            dk_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf, qb, dk_acc[db], 0, 0, 0);
           }
         }
-        // same-wave LDS visibility; A-operand reads below
-
-        // ---- dV += P^T @ dO ; dK += dS^T @ Q  (contraction over 32 q) ----
-        const bf16x8 ptf = *(const bf16x8*)(&pt_lds[row16][8 * grp]);
-        const bf16x8 dstf = *(const bf16x8*)(&dst_lds[row16][8 * grp]);
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          const bf16x8 dob = read_tr_frag(do_lds, db, lane);
-          const bf16x8 qb = read_tr_frag(q_lds, db, lane);
-          dv_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ptf, dob, dv_acc[db], 0, 0, 0);
-          dk_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dstf, qb, dk_acc[db], 0, 0, 0);
-        }
+        __syncthreads(); // staged tiles consumed before restage
       }
-      __syncthreads(); // staged tiles consumed before restage
-    }
+      if constexpr (kGqa) {
+        // (after the last head these four are formed and never read; with
+        // the exit test in front of them one SGPR spills in <false, true>)
+        ++g;
+        qp = tslice(q, sq, bh * group + g, H);
+        dop = tslice(dout, sdo, bh * group + g, H);
+        lsep = lse + (int64_t)(bh * group + g) * N;
+        delp = delta + (int64_t)(bh * group + g) * N;
+      }
+    } while (kGqa && g < group);
 
     if (valid) {
 #pragma unroll
@@ -767,13 +864,13 @@ __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dkdv_kernel(
 // ------------------------------------------------------------------- dQ
 // Mirror of the forward: block = 4 waves x one 16-q tile; 32-key KV tiles
 // (K and V staged shared). dq[q][d] += dS[q][key] @ K[key][d].
-template <bool kRagged, bool kDoc>
+template <bool kRagged, bool kDoc, bool kGqa>
 __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dq, int BH, int H, int N, float scale, bool causal_arg,
-    Strides sq, Strides sk, Strides sv, StridesDoc<kDoc> sdo) {
+    Strides sq, StridesGqa<kGqa> sk, Strides sv, StridesDoc<kDoc> sdo) {
   const bool causal = kDoc || causal_arg; // a document mask is causal by contract
   static_assert(kKT * kAttnD == kImgElems);
   __shared__ __hip_bfloat16 k_lds[kImgElems]; // tiled (vt_idx) image
@@ -792,8 +889,8 @@ __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dq_kernel(
     const int i0 = qb0 + wave * kQT;
     const bool valid = i0 < N;
     const __hip_bfloat16* qp = tslice(q, sq, bh, H);
-    const __hip_bfloat16* kp = tslice(k, sk, bh, H);
-    const __hip_bfloat16* vp = tslice(v, sv, bh, H);
+    const __hip_bfloat16* kp = kv_slice(k, sk, bh, H, sk);
+    const __hip_bfloat16* vp = kv_slice(v, sv, bh, H, sk);
     const __hip_bfloat16* dop = tslice(dout, sdo, bh, H);
     const float* lsep = lse + (int64_t)bh * N;
     const float* delp = delta + (int64_t)bh * N;
@@ -905,8 +1002,9 @@ __global__ void __launch_bounds__(kAttnThreads) attn_bwd_dq_kernel(
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Tensor o,
               at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor delta,
               double scale, bool causal, c10::optional<at::Tensor> doc_start) {
-  check_attn_args(q, {{"q", q}, {"k", k}, {"v", v}, {"dout", dout}},
-                  {{"o", o}, {"dq", dq}, {"dk", dk}, {"dv", dv}}, {{"lse", lse}, {"delta", delta}});
+  const int G = check_attn_args(q, k, {{"q", q}, {"dout", dout}}, {{"k", k}, {"v", v}},
+                                {{"o", o}, {"dq", dq}}, {{"dk", dk}, {"dv", dv}},
+                                {{"lse", lse}, {"delta", delta}});
   const int* dsp = checked_doc_start(doc_start, q, causal);
   const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
   auto stream = c10::hip::getCurrentHIPStream();
@@ -919,20 +1017,24 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
 
   // see crow(): <false> is the aligned code, for N that ends both kernels' blocks
   const bool ragged = N % kBwdKeysPerBlock != 0 || N % kDqRowsPerBlock != 0;
-  with_variant(ragged, dsp != nullptr, [&](auto ragged_c, auto doc) {
-    constexpr bool kRagged = decltype(ragged_c)::value, kDoc = decltype(doc)::value;
-    auto launch = [&](auto kernel, int rows_per_block, auto... outputs) {
-      hipLaunchKernelGGL(kernel, dim3(attn_grid(BH, N, rows_per_block)), dim3(kAttnThreads), 0,
+  with_variant(ragged, dsp != nullptr, G > 1, [&](auto ragged_c, auto doc, auto gqa) {
+    constexpr bool kRagged = decltype(ragged_c)::value, kDoc = decltype(doc)::value,
+                   kGqa = decltype(gqa)::value;
+    // grid_bh: the (b, head) pairs the kernel's blocks split: B * Hkv for
+    // dK/dV, B * H for dQ. The kernels themselves always take BH = B * H.
+    auto launch = [&](auto kernel, int grid_bh, int rows_per_block, auto... outputs) {
+      hipLaunchKernelGGL(kernel, dim3(attn_grid(grid_bh, N, rows_per_block)), dim3(kAttnThreads), 0,
                          stream, (const __hip_bfloat16*)q.data_ptr(),
                          (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
                          (const __hip_bfloat16*)dout.data_ptr(), lse.data_ptr<float>(),
                          delta.data_ptr<float>(), outputs..., BH, H, N, (float)scale, causal,
-                         strides_of(q), strides_of(k), strides_of(v),
+                         strides_of(q), gqa_strides_of<kGqa>(k, G), strides_of(v),
                          doc_strides_of<kDoc>(dout, dsp));
     };
-    launch(attn_bwd_dkdv_kernel<kRagged, kDoc>, kBwdKeysPerBlock, (__hip_bfloat16*)dk.data_ptr(),
-           (__hip_bfloat16*)dv.data_ptr());
-    launch(attn_bwd_dq_kernel<kRagged, kDoc>, kDqRowsPerBlock, (__hip_bfloat16*)dq.data_ptr());
+    launch(attn_bwd_dkdv_kernel<kRagged, kDoc, kGqa>, BH / G, kBwdKeysPerBlock,
+           (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr());
+    launch(attn_bwd_dq_kernel<kRagged, kDoc, kGqa>, BH, kDqRowsPerBlock,
+           (__hip_bfloat16*)dq.data_ptr());
   });
 }
 

@@ -14,6 +14,14 @@ ladder in profiles/ uses this switch). Numerics are verified in
 tests/test_gpu.py and tests/test_gpu_attention_ragged.py (shared
 helpers: tests/attn_testlib.py).
 
+Grouped-query attention: k and v may have fewer heads than q,
+[B, Hkv, N, 64] with Hkv dividing H (MQA is Hkv = 1). Query head h reads
+K/V head h // (H // Hkv): the layout of `enable_gqa=True` and of
+`repeat_interleave(H // Hkv, dim=1)`. The native kernels read the shared
+K/V heads in place and sum a group's dK/dV in their fp32 accumulators, so
+k.grad and v.grad come back in k's shape with one rounding; the fallback
+passes `enable_gqa=True`. Verified in tests/test_gpu_attention_gqa.py.
+
 Packed sequences: `sdpa(q, k, v, causal=True, doc_start=ds)` keeps
 attention inside documents when several are packed into one batch row.
 `ds` is an int32 [B, N] tensor, shared by all heads: ds[b, i] is the
@@ -59,8 +67,9 @@ class _SdpaFn(torch.autograd.Function):
         if dout.stride(-1) != 1:
             dout = dout.contiguous()
         dq = torch.empty(B, H, N, D, dtype=q.dtype, device=q.device)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
+        # k's shape: [B, Hkv, N, D] under grouped-query attention
+        dk = torch.empty(k.shape, dtype=q.dtype, device=q.device)
+        dv = torch.empty(k.shape, dtype=q.dtype, device=q.device)
         delta = torch.empty(B * H * N, dtype=torch.float32, device=q.device)
         _C.attn_bwd(q, k, v, dout, o, lse, dq, dk, dv, delta, ctx.scale, ctx.causal, doc_start)
         return dq, dk, dv, None, None, None
@@ -72,8 +81,9 @@ _INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
 def _usable(q, k, v, doc_start=None, causal=True):
     if not fused_attention_enabled():
         return False
-    # The kernels assume self-attention geometry: k/v must match q exactly
-    # (cross-attention with a different kv length/head count falls back).
+    # The kernels assume self-attention geometry: k/v must match q in every
+    # dim but the heads (cross-attention with a different kv length falls
+    # back), where k's and v's common count must divide q's (GQA/MQA).
     ok = (
         q.is_cuda
         and is_available()
@@ -81,8 +91,12 @@ def _usable(q, k, v, doc_start=None, causal=True):
         and q.dim() == 4
         and q.shape[-1] == 64
         and q.shape[-2] >= 1
-        and k.shape == q.shape
-        and v.shape == q.shape
+        and k.dim() == 4
+        and k.shape[0] == q.shape[0]
+        and k.shape[2:] == q.shape[2:]
+        and k.shape[1] >= 1
+        and q.shape[1] % k.shape[1] == 0
+        and v.shape == k.shape
         and k.dtype == q.dtype
         and v.dtype == q.dtype
         and k.device == q.device
@@ -104,8 +118,9 @@ def _usable(q, k, v, doc_start=None, causal=True):
 def fused_attention_usable(q, k, v, doc_start=None, causal=True) -> bool:
     """True when `sdpa(q, k, v, causal, doc_start)` will run the native
     MFMA kernels, False when it will fall back to torch SDPA: exactly the
-    decision `sdpa` makes (bf16 device tensors, [B, H, N, 64] with any
-    N >= 1, k and v shaped like q, extension built, no
+    decision `sdpa` makes (bf16 device tensors, q [B, H, N, 64] with any
+    N >= 1, k and v shaped like q or, for grouped-query attention, alike
+    with a head count that divides H, extension built, no
     DMLCLOUD_DISABLE_FUSED_ATTN; with a `doc_start` also causal=True and
     an integer [B, N] tensor on q's device). `causal` only matters when
     `doc_start` is given."""
@@ -193,7 +208,10 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
     copy.
 
     `doc_start` (integer [B, N], see the module docstring) restricts
-    attention to the query's own document. It takes no gradient."""
+    attention to the query's own document. It takes no gradient.
+
+    k and v may have fewer heads than q (grouped-query attention, see the
+    module docstring), on the native path and on the fallback alike."""
     if _usable(q, k, v, doc_start, causal):
         scale = 1.0 / math.sqrt(q.shape[-1])
         q = q if _lastdim_ok(q) else q.contiguous()
@@ -204,9 +222,12 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
         # no-ops for the int32 contiguous tensor document_starts() returns
         doc_start = doc_start.detach().to(torch.int32).contiguous()
         return _SdpaFn.apply(q, k, v, causal, scale, doc_start)
+    # enable_gqa only where the head counts differ: the plain call is
+    # exactly what it was
+    gqa = {'enable_gqa': True} if q.dim() == 4 and k.dim() == 4 and k.shape[1] != q.shape[1] else {}
     if doc_start is None:
-        return F.scaled_dot_product_attention(q, k, v, is_causal=causal)
-    return F.scaled_dot_product_attention(q, k, v, attn_mask=document_mask(doc_start, causal))
+        return F.scaled_dot_product_attention(q, k, v, is_causal=causal, **gqa)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=document_mask(doc_start, causal), **gqa)
 
 
 def fused_attention_enabled() -> bool:

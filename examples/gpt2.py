@@ -7,12 +7,17 @@ sync, hipGraph-captured steps inside a TrainValStage.
 Run:  python examples/gpt2.py
       torchrun --standalone --nproc-per-node 8 examples/gpt2.py
       python examples/gpt2.py --packed    # several documents per row
+      python examples/gpt2.py --n-kv-head 4   # grouped-query attention
 
 --packed fills every row with random-length documents that end in an EOS
 token, keeps attention inside each document (ops.fused_attn: the native
 kernels skip the tiles of other documents) and restarts the positions at
 every document start. The last token of a document has no next token of
 its own, so its target is the loss's ignore_index.
+
+--n-kv-head gives K and V that many heads (a divisor of the model's
+n_head; 1 is multi-query attention): the native kernels read the shared
+K/V heads in place and sum each group's dK/dV in registers.
 """
 
 import argparse
@@ -79,13 +84,14 @@ def packed_targets(idx: torch.Tensor, doc_start: torch.Tensor) -> torch.Tensor:
 
 
 class GPT2Stage(TrainValStage):
-    def __init__(self, packed: bool = False):
+    def __init__(self, packed: bool = False, n_kv_head: int = None):
         super().__init__()
         self.packed = packed
+        self.n_kv_head = n_kv_head
 
     def pre_stage(self):
         on_gpu = self.device.type == 'cuda'
-        model = gpt2_small() if on_gpu else gpt2_tiny()
+        model = (gpt2_small if on_gpu else gpt2_tiny)(n_kv_head=self.n_kv_head)
         dtype = torch.bfloat16 if on_gpu else torch.float32
         self.pipeline.register_model('gpt2', model, ddp_impl='flat', flat_dtype=dtype)
         replica = self.pipeline.models['gpt2']
@@ -135,11 +141,14 @@ class GPT2Stage(TrainValStage):
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     parser.add_argument('--packed', action='store_true', help='pack several documents into each row')
+    parser.add_argument(
+        '--n-kv-head', type=int, default=None, help='K/V heads for grouped-query attention (divides n_head)'
+    )
     args = parser.parse_args()
 
     init_process_group_auto()
     pipeline = TrainingPipeline(name='gpt2-synthetic')
-    pipeline.append_stage(GPT2Stage(packed=args.packed), max_epochs=MAX_EPOCHS)
+    pipeline.append_stage(GPT2Stage(packed=args.packed, n_kv_head=args.n_kv_head), max_epochs=MAX_EPOCHS)
     pipeline.run()
 
 

@@ -2,7 +2,14 @@
 aligned shapes plus one ragged sequence length (N=1000), plus packed
 sequences (document mask) at the GPT-2 shape: the native kDoc kernels
 beside the dense native causal kernels and beside torch SDPA given the
-equivalent boolean attn_mask."""
+equivalent boolean attn_mask; plus grouped-query attention (bench_gqa):
+the native kGqa kernels beside repeat_interleave + the native MHA kernels,
+torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
+
+    python tools/bench_attn.py            # every section
+    python tools/bench_attn.py --no-gqa   # the sections before GQA
+    python tools/bench_attn.py --gqa      # the GQA section alone
+"""
 
 import math
 import os
@@ -136,7 +143,58 @@ def bench_doc(b, h, n, d=64):
             )
 
 
+def bench_gqa(b, h, hkv, n, d=64):
+    """Causal forward and backward with `hkv` K/V heads for `h` query
+    heads, every native column through `sdpa`: native GQA | what a user
+    had before (repeat_interleave + native MHA; the forward times the
+    expansion, the backward autograd's sum over the group) | torch SDPA
+    with enable_gqa=True | native MHA at the same H on already expanded
+    K/V (the same FLOPs, no expansion: the cost to compare against)."""
+    from dmlcloud_amd.ops.fused_attn import fused_attention_usable, sdpa
+
+    g = h // hkv
+    torch.manual_seed(0)
+    mk = lambda heads: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16).requires_grad_(True)
+    q, k, v = mk(h), mk(hkv), mk(hkv)
+    ke, ve = mk(h), mk(h)
+    do = (torch.randn(b, h, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    assert fused_attention_usable(q, k, v) and fused_attention_usable(q, ke, ve)
+
+    forwards = {
+        'gqa': lambda: sdpa(q, k, v, causal=True),
+        'expand': lambda: sdpa(q, k.repeat_interleave(g, 1), v.repeat_interleave(g, 1), causal=True),
+        'torch': lambda: torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=True),
+        'mha': lambda: sdpa(q, ke, ve, causal=True),
+    }
+    t_fwd, t_bwd = {}, {}
+    for name, fwd in forwards.items():
+        with torch.no_grad():
+            t_fwd[name] = time_fn(fwd)
+        out = fwd()
+
+        def bwd():
+            q.grad = k.grad = v.grad = ke.grad = ve.grad = None
+            out.backward(do, retain_graph=True)
+
+        t_bwd[name] = time_fn(bwd, reps=20)
+    for tag, t in (('GQA FWD', t_fwd), ('GQA BWD', t_bwd)):
+        print(
+            f'{tag} B={b} H={h} Hkv={hkv} N={n}: gqa {t["gqa"]:8.1f}us | expand+mha {t["expand"]:8.1f}us '
+            f'({t["expand"] / t["gqa"]:4.2f}x) | torch gqa {t["torch"]:8.1f}us ({t["torch"] / t["gqa"]:4.2f}x) '
+            f'| mha H={h} {t["mha"]:8.1f}us ({t["mha"] / t["gqa"]:4.2f}x)'
+        )
+
+
+def main_gqa():
+    bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
+    bench_gqa(64, 12, 1, 1024)  # ... and as MQA
+    bench_gqa(16, 16, 2, 2048)  # 1024 dK/dV blocks, each 8 heads long
+
+
 if __name__ == '__main__':
+    if '--gqa' in sys.argv[1:]:
+        main_gqa()
+        sys.exit(0)
     bench(64, 12, 1024)  # the GPT-2 bench shape
     bench(64, 12, 1024, causal=False)
     bench(16, 16, 2048)
@@ -150,3 +208,6 @@ if __name__ == '__main__':
     bench_bwd(64, 12, 1000)
     # packed sequences at the GPT-2 shape (needs the doc_start bindings)
     bench_doc(64, 12, 1024)
+    # grouped-query attention (needs the kGqa kernels)
+    if '--no-gqa' not in sys.argv[1:]:
+        main_gqa()
