@@ -16,17 +16,24 @@ gives K and V fewer heads than Q. `c_attn` then projects to
 `n_embd + 2 * n_kv_head * head_dim` features and query head h reads K/V
 head h // (n_head // n_kv_head). `None` (or `n_head`) is plain GPT-2,
 unchanged.
+
+Sampling: `GPT2.generate(idx, max_new_tokens)` prefills a per-layer K/V
+cache (`init_cache`) from the prompt through the same `sdpa` path as
+training and then decodes one token per `decode_step` through
+ops.fused_attn.sdpa_kvcache, the split-KV decode kernels. The cache
+lengths live on the device and are advanced there, so a step has no host
+sync.
 """
 
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional
 
 import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..ops.fused_attn import document_starts, sdpa
+from ..ops.fused_attn import document_starts, sdpa, sdpa_kvcache
 from ..ops.fused_ln import LayerNorm
 from ..ops.fused_loss import cross_entropy
 
@@ -69,6 +76,33 @@ class CausalSelfAttention(nn.Module):
         y = y.transpose(1, 2).reshape(B, T, C)
         return self.c_proj(y)
 
+    def _heads(self, x):
+        B, T, C = x.shape
+        q, k, v = self.c_attn(x).split([C, self.kv_dim, self.kv_dim], dim=2)
+        q = q.view(B, T, self.n_head, C // self.n_head).transpose(1, 2)
+        k = k.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
+        v = v.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
+        return q, k, v
+
+    def prefill(self, x, k_cache, v_cache):
+        """forward(x) that also copies the prompt's K/V into cache rows 0..T-1."""
+        B, T, C = x.shape
+        q, k, v = self._heads(x)
+        k_cache[:, :, :T] = k
+        v_cache[:, :, :T] = v
+        return self.c_proj(sdpa(q, k, v, causal=True).transpose(1, 2).reshape(B, T, C))
+
+    def decode(self, x, k_cache, v_cache, kv_len, batch, pos):
+        """One new token per row, x [B, 1, C]: its K/V go to cache row
+        pos[b] = kv_len[b] - 1 (an indexed device write), then it attends
+        the kv_len[b] valid rows."""
+        B, _, C = x.shape
+        q, k, v = self._heads(x)
+        k_cache[batch, :, pos] = k[:, :, 0]
+        v_cache[batch, :, pos] = v[:, :, 0]
+        y = sdpa_kvcache(q, k_cache, v_cache, kv_len, causal=True)
+        return self.c_proj(y.transpose(1, 2).reshape(B, 1, C))
+
 
 class Block(nn.Module):
     def __init__(self, cfg: GPT2Config):
@@ -86,6 +120,24 @@ class Block(nn.Module):
         x = x + self.attn(self.ln_1(x), doc_start)
         x = x + self.mlp(self.ln_2(x))
         return x
+
+    def prefill(self, x, k_cache, v_cache):
+        x = x + self.attn.prefill(self.ln_1(x), k_cache, v_cache)
+        return x + self.mlp(self.ln_2(x))
+
+    def decode(self, x, *cache_args):
+        x = x + self.attn.decode(self.ln_1(x), *cache_args)
+        return x + self.mlp(self.ln_2(x))
+
+
+@dataclass
+class KVCache:
+    """Per-layer K and V, [B, n_kv_head, max_len, head_dim] each, and the
+    number of valid rows of every batch row, int32 [B] on the device."""
+
+    k: List[torch.Tensor]
+    v: List[torch.Tensor]
+    kv_len: torch.Tensor
 
 
 class GPT2(nn.Module):
@@ -135,6 +187,67 @@ class GPT2(nn.Module):
         # fused online-softmax CE on gfx950 for bf16 logits
         loss = cross_entropy(logits.view(-1, logits.size(-1)), targets.reshape(-1))
         return logits, loss
+
+    def init_cache(self, batch, max_len, device=None, dtype=None) -> KVCache:
+        """An empty cache for `batch` rows of up to `max_len` tokens."""
+        cfg = self.cfg
+        device = self.wte.weight.device if device is None else device
+        dtype = self.wte.weight.dtype if dtype is None else dtype
+        n_kv_head = cfg.n_head if cfg.n_kv_head is None else cfg.n_kv_head
+        shape = (batch, n_kv_head, max_len, cfg.n_embd // cfg.n_head)
+        return KVCache(
+            k=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
+            v=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
+            kv_len=torch.zeros(batch, dtype=torch.int32, device=device),
+        )
+
+    @torch.no_grad()
+    def prefill(self, idx, cache: KVCache):
+        """Run the prompt idx [B, T] through the training attention path,
+        fill the cache with its K/V and return the last position's logits
+        [B, vocab]."""
+        B, T = idx.shape
+        x = self.wte(idx) + self.wpe(torch.arange(T, device=idx.device))
+        for block, k_cache, v_cache in zip(self.blocks, cache.k, cache.v):
+            x = block.prefill(x, k_cache, v_cache)
+        cache.kv_len.fill_(T)
+        return self.lm_head(self.ln_f(x[:, -1]))
+
+    @torch.no_grad()
+    def decode_step(self, tokens, cache: KVCache):
+        """Append one token per row (tokens [B]) to the cache and return
+        the logits [B, vocab] for the token after it. Positions come from
+        cache.kv_len on the device; nothing is read back."""
+        B = tokens.shape[0]
+        pos = cache.kv_len.long()  # the new token's row, before the increment
+        cache.kv_len += 1
+        batch = torch.arange(B, device=tokens.device)
+        x = self.wte(tokens.view(B, 1)) + self.wpe(pos.clamp(max=self.cfg.n_positions - 1)).unsqueeze(1)
+        for block, k_cache, v_cache in zip(self.blocks, cache.k, cache.v):
+            # (a full cache overwrites its last row instead of writing past it)
+            x = block.decode(x, k_cache, v_cache, cache.kv_len, batch, pos.clamp(max=k_cache.shape[2] - 1))
+        return self.lm_head(self.ln_f(x[:, 0]))
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None):
+        """idx [B, T] followed by max_new_tokens sampled tokens,
+        [B, T + max_new_tokens]. temperature = 0 is greedy; otherwise the
+        next token is drawn from softmax(logits / temperature)."""
+        B, T = idx.shape
+        assert T >= 1 and T + max_new_tokens <= self.cfg.n_positions, 'sequence exceeds n_positions'
+        cache = self.init_cache(B, T + max_new_tokens)
+        out = [idx]
+        logits = self.prefill(idx, cache)
+        for step in range(max_new_tokens):
+            if step > 0:
+                logits = self.decode_step(out[-1].view(B), cache)
+            if temperature == 0.0:
+                nxt = logits.argmax(dim=-1, keepdim=True)
+            else:
+                probs = torch.softmax(logits.float() / temperature, dim=-1)
+                nxt = torch.multinomial(probs, 1, generator=generator)
+            out.append(nxt)
+        return torch.cat(out, dim=1)
 
 
 def gpt2_small(n_kv_head: Optional[int] = None) -> GPT2:

@@ -261,5 +261,7 @@ from .fused_attn import (  # noqa: E402,F401
     document_starts_from_eos,
     fused_attention_enabled,
     fused_attention_usable,
+    fused_kvcache_usable,
     sdpa,
+    sdpa_kvcache,
 )

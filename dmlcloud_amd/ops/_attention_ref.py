@@ -432,3 +432,42 @@ def gqa_bwd_padded(do, q, k, v, o, lse, causal=True, scale=None, doc_start=None)
                     dv[b, kvh][key_g[keep]] = dv_acc[keep]
                     dk[b, kvh][key_g[keep]] = dk_acc[keep]
     return dq, dk, dv
+
+
+# ---------------------------------------------------------------------------
+# KV-cache decode: the reference of ops.fused_attn.sdpa_kvcache
+# ---------------------------------------------------------------------------
+
+
+def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=False):
+    """fp32 masked softmax of a few new query rows over the valid part of a
+    K/V cache: the CPU path and the test oracle of `sdpa_kvcache`.
+
+    q [B, H, Nq, D]; k_cache, v_cache [B, Hkv, Nmax, D], query head h reads
+    K/V head h // (H // Hkv); kv_len integer [B], clamped like the kernels
+    do ([Nq, Nmax] causal, [1, Nmax] otherwise). Query row i of batch row b
+    sits at p = kv_len[b] - Nq + i and attends keys 0..p (causal) or
+    0..kv_len[b] - 1. Cache rows at or past kv_len[b] may hold anything,
+    NaN included: their scores are replaced and their V rows zeroed before
+    any product. Returns o in q's dtype (and lse [B, H, Nq] fp32)."""
+    B, H, Nq, D = q.shape
+    Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
+    assert v_cache.shape == k_cache.shape and H % Hkv == 0 and Nmax >= Nq
+    G = H // Hkv
+    ln = kv_len.long().clamp(Nq if causal else 1, Nmax)  # [B]
+    keys = torch.arange(Nmax, device=q.device)
+    if causal:
+        last = ln[:, None] - Nq + torch.arange(Nq, device=q.device)[None, :]  # [B, Nq]
+    else:
+        last = (ln - 1)[:, None].expand(B, Nq)
+    dead = keys[None, None, :] > last[:, :, None]  # [B, Nq, Nmax]
+    slack = keys[None, :] >= ln[:, None]  # [B, Nmax]
+
+    qg = q.float().reshape(B, Hkv, G, Nq, D)
+    s = torch.einsum('bkgqd,bknd->bkgqn', qg, k_cache.float()) / math.sqrt(D)
+    s = s.masked_fill(dead[:, None, None], -float('inf'))
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    vf = v_cache.float().masked_fill(slack[:, None, :, None], 0.0)
+    o = torch.einsum('bkgqn,bknd->bkgqd', p, vf).reshape(B, H, Nq, D).to(q.dtype)
+    return (o, lse.reshape(B, H, Nq)) if return_lse else o

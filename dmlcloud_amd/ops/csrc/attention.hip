@@ -8,6 +8,9 @@
 //                         stream past. Emits dK, dV.
 //   attn_bwd_dq_kernel    wave owns 16 q rows, block 64; 32-key K/V tiles
 //                         stream past. Emits dQ.
+//   attn_decode_split_kernel / attn_decode_merge_kernel: a few new q rows
+//                         over a K/V cache with device-resident lengths,
+//                         keys split over blocks (see "KV-cache decode").
 // Fragment maps of v_mfma_f32_16x16x32_bf16, empirically confirmed
 // (profiles/mfma_16x16x32_bf16_layout.txt):
 //   A (bf16x8): lane l elem j <-> A[l%16][8*(l/16)+j]
@@ -1036,6 +1039,444 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
     launch(attn_bwd_dq_kernel<kRagged, kDoc, kGqa>, BH, kDqRowsPerBlock,
            (__hip_bfloat16*)dq.data_ptr());
   });
+}
+
+// ===========================================================================
+// KV-cache decode: split-KV forward + merge (ops.fused_attn.sdpa_kvcache)
+// ===========================================================================
+//
+// q [B, H, Nq, 64] holds a few NEW rows, k/v [B, Hkv, Nmax, 64] a cache of
+// which batch row b has kv_len[b] valid rows (the new tokens' included), an
+// int32 read from device memory. Query row i sits at position
+// p = len - Nq + i and attends keys 0..p (causal, bottom-right aligned) or
+// 0..len-1, with len = decode_len(): kv_len[b] clamped so that every row
+// keeps a key and no index leaves the cache, whatever the tensor holds (the
+// dstart() rule). Decode reads K and V once and does ~1 flop per byte, so
+// the work split is made for bytes in flight, not for the MFMA rate:
+//   * the 16 MFMA query COLUMNS of S^T = K Q^T belong to ONE K/V head: the
+//     R = G * Nq <= 16 pairs c = g * Nq + i (query head kvh * G + g, row i).
+//     Columns >= R re-read column R - 1 and are never stored;
+//   * the keys are split over S blocks per (b, K/V head), each a contiguous
+//     chunk (a multiple of 128 keys); inside a chunk wave w walks the 32-key
+//     tiles w, w + 4, ... on its own: no barrier in the key loop, its own
+//     running (m, l) and 16x64 fp32 O accumulator;
+//   * K needs no LDS: the A fragment K[key0 + l%16][32c + 8(l/16)..+7] is a
+//     16-byte global load per lane. V goes through a per-wave double-buffered
+//     32x64 tiled image and read_tr_frag, P through a per-wave LDS slice;
+//   * the loads of the wave's NEXT tile are issued before the current
+//     tile's math and written to the other image after it;
+//   * EVERY key-row index is clamped to len - 1. Masking the score is not
+//     enough: the cache rows >= len are uninitialised by contract, and
+//     P = 0 times a NaN V row is NaN inside the MFMA, so they are never read;
+//   * the four waves' (m, l, O) meet once, in LDS, behind one barrier, and
+//     are combined in wave order. S == 1: the block normalises and stores.
+//     S > 1: it writes one fp32 partial to the workspace,
+//     O [B, Hkv, S, 16, 64] then (m, l) [B, Hkv, S, 16, 2], and
+//     attn_decode_merge_kernel combines the LIVE splits in ascending order.
+//     No atomics: results are bitwise repeatable for a (shape, S).
+// kDecodeFn: this code is compiled without packed-fp32 instructions (its
+// rescales are the natural candidates for them). A function built for
+// another feature set is only inlined into it when it is always_inline, so
+// everything called below is __forceinline__, a builtin, or one of the three
+// helpers that stand in for __shfl, __shfl_xor and __syncthreads.
+#define kDecodeFn __attribute__((target("no-packed-fp32-ops")))
+
+// the value `x` of lane `src` (0..63), as __shfl does it
+kDecodeFn __device__ __forceinline__ float decode_shfl(float x, int src) {
+  return __builtin_bit_cast(float,
+                            __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, x)));
+}
+kDecodeFn __device__ __forceinline__ void decode_barrier() { // __syncthreads()
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+constexpr int kDecCols = 16; // query columns of one block (one MFMA tile)
+constexpr int kDecChunkAlign = kWavesPerBlock * kKT; // 128: a chunk gives every wave whole tiles
+constexpr int kDecPartO = kDecCols * kAttnD; // floats of one O partial
+constexpr int kDecPartML = kDecCols * 2; // floats of one (m, l) partial
+
+// A wave's LDS: its two V images during the key loop, its (m, l, O) for the
+// block epilogue after it (only the wave itself writes either).
+union DecodeWaveLds {
+  __bf16 v[2][kImgElems];
+  struct {
+    float o[kDecCols][kAttnD];
+    float ml[kDecCols][2];
+  } part;
+};
+constexpr int kDecWaveLdsFloats = sizeof(DecodeWaveLds) / sizeof(float);
+
+// The value both kernels use for kv_len[b]: at least one key per stored row
+// (Nq rows need positions 0..Nq-1 when causal), at most the cache.
+kDecodeFn __device__ __forceinline__ int decode_len(const int* __restrict__ kv_len, int b, int Nq,
+                                                    int Nmax, bool causal) {
+  return min(max(kv_len[b], causal ? Nq : 1), Nmax);
+}
+
+// Thread tid of a 256-thread block owns column tid / 16 and the four head-dim
+// elements 4 * (tid % 16).. of the combined result.
+struct DecodeAcc {
+  float m, l; // log2-domain running max, sum of exp2
+  f32x4 o; // unnormalised
+};
+
+// Combine `n` partials (O at o_parts + s * o_stride, (m, l) at ml_parts +
+// s * ml_stride) in ascending s. A partial whose column saw only masked keys
+// has m = -1e30 and finite garbage in l and O (the wipe, see the key loop);
+// beside a partial with a real maximum M its weight exp2(-1e30 - M) is
+// exactly 0. An empty partial (a wave without a tile) is m = -1e30, l = O = 0.
+kDecodeFn __device__ __forceinline__ DecodeAcc decode_combine(const float* o_parts,
+                                                              const float* ml_parts, int n,
+                                                              int o_stride, int ml_stride, int col,
+                                                              int d4) {
+  DecodeAcc a = {-1e30f, 0.0f, f32x4{0, 0, 0, 0}};
+  for (int s = 0; s < n; ++s) a.m = fmaxf(a.m, ml_parts[(int64_t)s * ml_stride + 2 * col]);
+  for (int s = 0; s < n; ++s) {
+    const float* ml = ml_parts + (int64_t)s * ml_stride + 2 * col;
+    const float w = __builtin_amdgcn_exp2f(ml[0] - a.m);
+    const f32x4 po = *(const f32x4*)(o_parts + (int64_t)s * o_stride + col * kAttnD + d4);
+    a.l += w * ml[1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a.o[r] += w * po[r];
+  }
+  return a;
+}
+
+// Normalise and store column `col` (< R) of K/V head kvh: o bf16, lse fp32.
+kDecodeFn __device__ __forceinline__ void decode_store(const DecodeAcc& a,
+                                                       __hip_bfloat16* __restrict__ o,
+                                                       float* __restrict__ lse, int b, int kvh,
+                                                       int H, int G, int Nq, int col, int d4) {
+  const int g = col / Nq;
+  const int64_t row = ((int64_t)b * H + kvh * G + g) * Nq + (col - g * Nq);
+  bf16x4 ov;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ov[r] = (__bf16)(a.o[r] / a.l);
+  *(bf16x4*)(o + row * kAttnD + d4) = ov;
+  if (d4 == 0) lse[row] = kLn2 * a.m + __logf(a.l); // log2 domain -> natural log
+}
+
+kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_split_kernel(
+    const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
+    const __hip_bfloat16* __restrict__ v, const int* __restrict__ kv_len,
+    __hip_bfloat16* __restrict__ o, float* __restrict__ lse, float* __restrict__ ws_o,
+    float* __restrict__ ws_ml, int H, int G, int Nq, int Nmax, int S, int chunk, float scale,
+    bool causal, Strides sq, Strides sk, Strides sv) {
+  static_assert(kKT * kAttnD == kImgElems);
+  __shared__ DecodeWaveLds wave_lds[kWavesPerBlock];
+  __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStride];
+
+  // plain ints, not a structured binding: the tile lambdas capture them
+  const Coords tc = thread_coords();
+  const int lane = tc.lane, row16 = tc.row16, grp = tc.grp, st_col = tc.st_col;
+  const int wave = __builtin_amdgcn_readfirstlane(tc.wave);
+  __hip_bfloat16(*p_lds)[kPStride] = p_lds_all[wave];
+  const __hip_bfloat16* v_img = (const __hip_bfloat16*)wave_lds[wave].v[0]; // image b at + b * kImgElems
+  // V staging: the WAVE moves a 32x64 tile as 4 bf16x8 pieces per lane,
+  // rows st_row + 8x, columns st_col..+7
+  const int st_row = lane >> 3;
+
+  // grid: (b, K/V head, split), split fastest
+  const int Hkv = H / G;
+  const int s = blockIdx.x % S;
+  const int kvh = (blockIdx.x / S) % Hkv;
+  const int b = blockIdx.x / S / Hkv;
+  const int R = G * Nq;
+  const int len = decode_len(kv_len, b, Nq, Nmax, causal);
+
+  // Which keys are walked, and why every stored column sees its own keys.
+  // Split s owns keys [s * chunk, (s + 1) * chunk), S * chunk >= Nmax >= len
+  // (launcher), and needs those below len: k_end. A split with
+  // k_begin >= len has none and returns before the barrier, all threads
+  // alike (block-uniform), writing nothing; the merge kernel derives the
+  // same live count from the same len and never reads its partial. Wave w
+  // walks the tiles key0 = k_begin + 32 * (w + 4t) < k_end (wave-uniform),
+  // so any key j < len is walked exactly once: by the split s = j / chunk
+  // (k_begin <= j < len: live) in the tile key0 = j - (j - k_begin) % 32
+  // <= j < k_end. A stored column at position p (0 <= p < len, because
+  // len >= Nq when causal) therefore meets all of its keys 0..p (causal) or
+  // 0..len-1, and nothing else counts: a score with key > lim is -1e30.
+  // Key 0 is unmasked for every column and sits in split 0, wave 0, tile 0,
+  // which is always walked (len >= 1), so the merged maximum of a stored
+  // column is a real score and its l is >= 1 term of exp2(0).
+  // The wipe: in a split s > 0 (or a wave's early tiles) a causal column
+  // with p < key0 sees only -1e30: m stays -1e30, alpha = exp2(0) = 1 and
+  // every p = exp2(0) = 1, so l and O collect finite garbage (the V rows
+  // are real rows < len). Wherever that meets a real maximum M (a later
+  // tile, another wave, another split) its factor is exp2(-1e30 - M) = 0.
+  const int k_begin = s * chunk;
+  if (k_begin >= len) return;
+  const int k_end = min(k_begin + chunk, len);
+
+  // this lane's query column: Q B-fragments, and the last key it attends
+  const int col_q = min(row16, R - 1);
+  const int g_q = col_q / Nq;
+  const int i_q = col_q - g_q * Nq;
+  const int lim = causal ? len - Nq + i_q : len - 1;
+  const __hip_bfloat16* qp = q + (int64_t)b * sq.b + (int64_t)(kvh * G + g_q) * sq.h + (int64_t)i_q * sq.r;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) qf[c] = *(const bf16x8*)(qp + 32 * c + 8 * grp);
+
+  const __hip_bfloat16* kp = k + (int64_t)b * sk.b + (int64_t)kvh * sk.h;
+  const __hip_bfloat16* vp = v + (int64_t)b * sv.b + (int64_t)kvh * sv.h;
+  // K fragments [16-key half h][k-chunk c] and V pieces of the tile at key0,
+  // every row clamped to len - 1
+  auto load_tile = [&](int key0, bf16x8(&kf)[2][2], bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t kr = min(key0 + 16 * h + row16, len - 1);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) kf[h][c] = *(const bf16x8*)(kp + kr * sk.r + 32 * c + 8 * grp);
+    }
+    // K before V, pinned: loads return in order, so the wait in front of
+    // the V image writes (after the math) also covers K, and the MFMAs at
+    // the top of the next tile wait for nothing. With V first the compiler
+    // put a full wait for the NEXT tile's loads in front of this tile's math.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int64_t vr = min(key0 + st_row + 8 * x, len - 1);
+      vpc[x] = *(const bf16x8*)(vp + vr * sv.r + st_col);
+    }
+  };
+  auto stage_v = [&](int buf, const bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      *(bf16x8*)(&wave_lds[wave].v[buf][vt_idx(st_row + 8 * x, st_col)]) = vpc[x];
+    }
+  };
+
+  const float scale2 = scale * kLog2e; // fold log2(e): exp -> v_exp_f32
+  float m_run = -1e30f, l_run = 0.0f;
+  f32x4 o_acc[4];
+#pragma unroll
+  for (int db = 0; db < 4; ++db) o_acc[db] = f32x4{0, 0, 0, 0};
+
+  int key0 = k_begin + wave * kKT;
+  bool have = key0 < k_end;
+  bf16x8 kf[2][2], vpc[4];
+  if (have) {
+    load_tile(key0, kf, vpc);
+    stage_v(0, vpc);
+  }
+  int buf = 0;
+  while (have) {
+    // the next tile's loads stay in flight through this tile's math
+    const int key_next = key0 + kWavesPerBlock * kKT;
+    const bool has_next = key_next < k_end;
+    bf16x8 kf_next[2][2];
+    if (has_next) load_tile(key_next, kf_next, vpc);
+
+    // ---- S^T = K Q^T: rows = key (16h + 4grp + r), col = row16 ----
+    float sc[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[h][c], qf[c], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = acc[r] * scale2; // log2-domain score
+        // one compare: causal end, cache end and clamped duplicates alike
+        if (key0 + 16 * h + 4 * grp + r > lim) x = -1e30f;
+        sc[4 * h + r] = x;
+      }
+    }
+
+    // ---- online softmax (per column row16; reduce across the grp groups) ----
+    float mt = sc[0];
+#pragma unroll
+    for (int x = 1; x < 8; ++x) mt = fmaxf(mt, sc[x]);
+    mt = fmaxf(mt, decode_shfl(mt, lane ^ 16));
+    mt = fmaxf(mt, decode_shfl(mt, lane ^ 32));
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new); // -1e30 -> 0
+    float ps = 0.0f;
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+      sc[x] = __builtin_amdgcn_exp2f(sc[x] - m_new);
+      ps += sc[x];
+    }
+    ps += decode_shfl(ps, lane ^ 16);
+    ps += decode_shfl(ps, lane ^ 32);
+    l_run = l_run * alpha + ps;
+    m_run = m_new;
+
+    // ---- P^T -> the wave's LDS slice, back as the A operand ----
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      bf16x4 pw;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pw[r] = (__bf16)sc[4 * h + r];
+      *(bf16x4*)(&p_lds[row16][16 * h + 4 * grp]) = pw;
+    }
+    float a_o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a_o[r] = decode_shfl(alpha, 4 * grp + r);
+    const bf16x8 pf = *(const bf16x8*)(&p_lds[row16][8 * grp]);
+
+    // ---- O = alpha O + P V: rows = column (4grp + r), cols = 16db + row16 ----
+#pragma unroll
+    for (int db = 0; db < 4; ++db) {
+      const bf16x8 vf = read_tr_frag(v_img + buf * kImgElems, db, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o_acc[db][r] *= a_o[r];
+      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, o_acc[db], 0, 0, 0);
+    }
+
+    if (has_next) {
+      stage_v(buf ^ 1, vpc); // the image this tile did not read
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) kf[h][c] = kf_next[h][c];
+    }
+    key0 = key_next;
+    buf ^= 1;
+    have = has_next;
+  }
+
+  // ---- block epilogue: the waves' (m, l, O) through LDS, one barrier ----
+  // (a wave overwrites its OWN images, after its own last read of them)
+#pragma unroll
+  for (int db = 0; db < 4; ++db) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wave_lds[wave].part.o[4 * grp + r][16 * db + row16] = o_acc[db][r];
+  }
+  if (lane < kDecCols) {
+    wave_lds[wave].part.ml[row16][0] = m_run;
+    wave_lds[wave].part.ml[row16][1] = l_run;
+  }
+  decode_barrier();
+
+  const int col = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+  const DecodeAcc a =
+      decode_combine(&wave_lds[0].part.o[0][0], &wave_lds[0].part.ml[0][0], kWavesPerBlock,
+                     kDecWaveLdsFloats, kDecWaveLdsFloats, col, d4);
+  if (S == 1) {
+    if (col < R) decode_store(a, o, lse, b, kvh, H, G, Nq, col, d4);
+  } else {
+    // all 16 columns: the duplicates of column R - 1 are finite and unread
+    *(f32x4*)(ws_o + (int64_t)blockIdx.x * kDecPartO + col * kAttnD + d4) = a.o;
+    if (d4 == 0) {
+      ws_ml[(int64_t)blockIdx.x * kDecPartML + 2 * col] = a.m;
+      ws_ml[(int64_t)blockIdx.x * kDecPartML + 2 * col + 1] = a.l;
+    }
+  }
+}
+
+// One block per (b, K/V head): combine the partials of the splits that ran.
+// Split s ran iff s * chunk < len (the split kernel's early return), so
+// the live ones are 0..n_live-1 and no other partial is read (the workspace
+// is uninitialised behind them).
+kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_merge_kernel(
+    const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
+    const int* __restrict__ kv_len, __hip_bfloat16* __restrict__ o, float* __restrict__ lse,
+    int H, int G, int Nq, int Nmax, int S, int chunk, bool causal) {
+  const int Hkv = H / G;
+  const int kvh = blockIdx.x % Hkv;
+  const int b = blockIdx.x / Hkv;
+  const int len = decode_len(kv_len, b, Nq, Nmax, causal);
+  const int n_live = min(S, (len + chunk - 1) / chunk); // >= 1: len >= 1
+  const int col = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+  if (col >= G * Nq) return;
+  const DecodeAcc a = decode_combine(ws_o + (int64_t)blockIdx.x * S * kDecPartO,
+                                     ws_ml + (int64_t)blockIdx.x * S * kDecPartML, n_live,
+                                     kDecPartO, kDecPartML, col, d4);
+  decode_store(a, o, lse, b, kvh, H, G, Nq, col, d4);
+}
+
+static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+int64_t attn_decode_workspace_floats(int64_t B, int64_t Hkv, int64_t S) {
+  return S > 1 ? B * Hkv * S * (kDecPartO + kDecPartML) : 0; // S == 1 stores directly
+}
+
+// The split count a call runs with: `num_splits` when positive, else
+// S = clamp(ceil(2 * CUs / (B * Hkv)), 1, ceil(Nmax / 128)): about two blocks
+// per CU. It depends on the shapes and the device only, never on kv_len, so
+// a captured call keeps its grid. The factor 2 is a starting point, not a
+// measured optimum.
+int64_t attn_decode_splits(int64_t B, int64_t Hkv, int64_t Nmax, int64_t num_splits,
+                           int64_t device) {
+  const int64_t max_splits = ceil_div(Nmax, kDecChunkAlign);
+  TORCH_CHECK(B >= 1 && Hkv >= 1 && Nmax >= 1, "attn_decode: B, Hkv and Nmax must be >= 1");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= max_splits, "num_splits must lie in [0, ceil(Nmax / ",
+              kDecChunkAlign, ")] = [0, ", max_splits, "], got ", num_splits);
+  if (num_splits > 0) return num_splits;
+  int cus = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, (int)device) ==
+                      hipSuccess && cus > 0,
+              "attn_decode: cannot read the CU count of device ", device);
+  return std::min(std::max<int64_t>(ceil_div(2 * (int64_t)cus, B * Hkv), 1), max_splits);
+}
+
+void attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
+                 at::Tensor lse, at::Tensor ws, double scale, bool causal, int64_t num_splits) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1 &&
+                  q.scalar_type() == at::kBFloat16,
+              "q must be a bf16 device tensor [B,H,Nq,64] with Nq >= 1 (head dim 64 only)");
+  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2);
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == kAttnD && k.size(1) >= 1 &&
+                  H % k.size(1) == 0,
+              "k_cache must be [B,Hkv,Nmax,64] with q's B and a head count Hkv that divides q's: "
+              "got ", k.sizes(), " for q ", q.sizes());
+  const int64_t Hkv = k.size(1), Nmax = k.size(2), G = H / Hkv;
+  TORCH_CHECK(v.sizes() == k.sizes(), "v_cache must be shaped like k_cache");
+  TORCH_CHECK(G * Nq <= kDecCols, "attn_decode serves (H / Hkv) * Nq <= ", kDecCols, ", got ",
+              G * Nq);
+  TORCH_CHECK(Nmax >= Nq, "the cache must hold the Nq new rows: Nmax ", Nmax, " < Nq ", Nq);
+  TORCH_CHECK(Nmax <= INT32_MAX - 2 * kDecChunkAlign && B * H * Nq <= INT32_MAX,
+              "attn_decode: Nmax or B*H*Nq too large");
+  for (const NamedTensor& a : {NamedTensor{"q", q}, {"k_cache", k}, {"v_cache", v}}) {
+    const at::Tensor& t = a.second;
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.device() == q.device() && t.stride(3) == 1,
+                a.first, " must be bf16 on q's device with a contiguous last dim");
+    // rows are read as 16-byte vectors
+    TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+                    t.stride(2) % 8 == 0,
+                a.first, " must be 16-byte aligned with batch/head/row strides that are multiples "
+                         "of 8 elements");
+  }
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.device() == q.device() &&
+                  kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "kv_len must be int32 [B], contiguous, on q's device");
+  TORCH_CHECK(o.scalar_type() == at::kBFloat16 && o.device() == q.device() &&
+                  o.sizes() == q.sizes() && o.is_contiguous(),
+              "o must be bf16, shaped like q, contiguous, on q's device");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.device() == q.device() &&
+                  lse.numel() == B * H * Nq && lse.is_contiguous(),
+              "lse must be fp32 [B,H,Nq], contiguous, on q's device");
+  const int S = (int)attn_decode_splits(B, Hkv, Nmax, num_splits, q.get_device());
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.device() == q.device() && ws.is_contiguous() &&
+                  ws.numel() >= attn_decode_workspace_floats(B, Hkv, S) &&
+                  (ws.numel() == 0 || (uintptr_t)ws.data_ptr() % 16 == 0),
+              "the workspace must be fp32, contiguous, 16-byte aligned, on q's device, with >= ",
+              attn_decode_workspace_floats(B, Hkv, S), " elements for ", S, " splits");
+  TORCH_CHECK(B * Hkv * S <= INT32_MAX, "attn_decode: too many blocks");
+  // chunk: ceil(Nmax / S) rounded up to whole 4-wave rounds, so S * chunk >= Nmax
+  const int chunk = (int)(ceil_div(ceil_div(Nmax, S), kDecChunkAlign) * kDecChunkAlign);
+
+  auto stream = c10::hip::getCurrentHIPStream();
+  float* ws_o = S > 1 ? ws.data_ptr<float>() : nullptr;
+  float* ws_ml = S > 1 ? ws_o + B * Hkv * S * kDecPartO : nullptr;
+  hipLaunchKernelGGL(attn_decode_split_kernel, dim3((unsigned)(B * Hkv * S)), dim3(kAttnThreads), 0,
+                     stream, (const __hip_bfloat16*)q.data_ptr(),
+                     (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
+                     kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(),
+                     ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax, S, chunk, (float)scale, causal,
+                     strides_of(q), strides_of(k), strides_of(v));
+  if (S > 1) {
+    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)(B * Hkv)), dim3(kAttnThreads), 0,
+                       stream, (const float*)ws_o, (const float*)ws_ml, kv_len.data_ptr<int>(),
+                       (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(), (int)H, (int)G, (int)Nq,
+                       (int)Nmax, S, chunk, causal);
+  }
 }
 
 } // namespace dmlamd

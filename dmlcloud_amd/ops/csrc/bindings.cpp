@@ -70,6 +70,11 @@ void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor
 void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Tensor o,
               at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor delta,
               double scale, bool causal, c10::optional<at::Tensor> doc_start);
+void attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
+                 at::Tensor lse, at::Tensor ws, double scale, bool causal, int64_t num_splits);
+int64_t attn_decode_workspace_floats(int64_t B, int64_t Hkv, int64_t S);
+int64_t attn_decode_splits(int64_t B, int64_t Hkv, int64_t Nmax, int64_t num_splits,
+                           int64_t device);
 
 } // namespace dmlamd
 
@@ -120,4 +125,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"), py::arg("o"), py::arg("lse"),
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("delta"), py::arg("scale"),
         py::arg("causal"), py::arg("doc_start") = py::none());
+  m.def("attn_decode", &dmlamd::attn_decode,
+        "Split-KV decode attention over a K/V cache with device-resident int32 kv_len[B] "
+        "(MFMA bf16, D=64, (H/Hkv)*Nq <= 16; num_splits 0 = auto)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"), py::arg("o"),
+        py::arg("lse"), py::arg("ws"), py::arg("scale"), py::arg("causal"), py::arg("num_splits"));
+  m.def("attn_decode_workspace_floats", &dmlamd::attn_decode_workspace_floats,
+        "fp32 elements attn_decode's workspace needs for S splits", py::arg("B"), py::arg("Hkv"),
+        py::arg("S"));
+  m.def("attn_decode_splits", &dmlamd::attn_decode_splits,
+        "The split count attn_decode runs with (num_splits, or the automatic choice for 0)",
+        py::arg("B"), py::arg("Hkv"), py::arg("Nmax"), py::arg("num_splits"), py::arg("device"));
 }

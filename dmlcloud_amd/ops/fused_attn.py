@@ -36,6 +36,13 @@ documents are skipped, not masked). `document_starts(doc_ids)` and
 whenever the native path is not usable, the same mask is handed to
 torch SDPA as a boolean attn_mask. Verified in
 tests/test_gpu_attention_docmask.py.
+
+Decoding: `sdpa_kvcache(q, k_cache, v_cache, kv_len)` attends a few new
+query rows to a partly filled [B, Hkv, Nmax, 64] K/V cache whose per-row
+lengths live on the device. It has kernels of its own (split-KV decode
+plus a merge pass, ops/csrc/attention.hip) and never goes through `sdpa`,
+whose behaviour for kv length != q length (torch SDPA, top-left causal)
+is unchanged. Verified in tests/test_gpu_attention_kvcache.py.
 """
 
 import math
@@ -228,6 +235,93 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
     if doc_start is None:
         return F.scaled_dot_product_attention(q, k, v, is_causal=causal, **gqa)
     return F.scaled_dot_product_attention(q, k, v, attn_mask=document_mask(doc_start, causal), **gqa)
+
+
+def _kvcache_usable(q, k_cache, v_cache, kv_len):
+    if not fused_attention_enabled():
+        return False
+    return (
+        q.is_cuda
+        and is_available()
+        and q.dtype == torch.bfloat16
+        and q.dim() == 4
+        and q.shape[-1] == 64
+        and k_cache.dim() == 4
+        and k_cache.shape[0] == q.shape[0]
+        and k_cache.shape[3] == 64
+        and k_cache.shape[1] >= 1
+        and q.shape[1] % k_cache.shape[1] == 0
+        and 1 <= (q.shape[1] // k_cache.shape[1]) * q.shape[2] <= 16
+        and k_cache.shape[2] >= q.shape[2]
+        and v_cache.shape == k_cache.shape
+        and k_cache.dtype == q.dtype
+        and v_cache.dtype == q.dtype
+        and k_cache.device == q.device
+        and v_cache.device == q.device
+        and all(t.stride(-1) == 1 for t in (q, k_cache, v_cache))
+        and kv_len.dtype in _INT_DTYPES
+        and kv_len.shape == (q.shape[0],)
+        and kv_len.device == q.device
+    )
+
+
+def fused_kvcache_usable(q, k_cache, v_cache, kv_len) -> bool:
+    """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len)` will run the
+    native split-KV decode kernels, False when it will run the pure-torch
+    reference: bf16 device tensors, q [B, H, Nq, 64], caches
+    [B, Hkv, Nmax, 64] with Hkv dividing H, 1 <= (H / Hkv) * Nq <= 16,
+    Nmax >= Nq, last dims contiguous, an integer [B] kv_len on q's device,
+    extension built, no DMLCLOUD_DISABLE_FUSED_ATTN."""
+    return bool(_kvcache_usable(q, k_cache, v_cache, kv_len))
+
+
+def _vector_loadable(t):
+    # the kernels read rows as 16-byte vectors
+    return t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1])
+
+
+def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: int = 0, return_lse: bool = False):
+    """Attention of a few new query rows over a partly filled K/V cache
+    (decoding); forward only.
+
+    q is [B, H, Nq, D]; k_cache and v_cache are [B, Hkv, Nmax, D] with Hkv
+    dividing H (query head h reads K/V head h // (H // Hkv), as in `sdpa`);
+    kv_len is an integer [B] tensor on q's device: the number of valid
+    cache rows of each batch row, the Nq new tokens' rows (already
+    written by the caller) included. Query row i of batch row b sits at
+    position p = kv_len[b] - Nq + i and attends keys 0..p with causal=True
+    (bottom-right aligned) and keys 0..kv_len[b] - 1 otherwise. Cache rows
+    at or past kv_len[b] are never read. The value used for kv_len[b] is
+    clamped to [Nq, Nmax] (causal) or [1, Nmax].
+
+    On the native path (`fused_kvcache_usable`) the lengths are read on the
+    device: no host sync, hipGraph-capturable, and kv_len and the cache
+    contents may change between replays. The keys are split over
+    `num_splits` blocks per (b, K/V head), 0 = chosen from the shapes and
+    the device's CU count, and merged by a second kernel; any batch / head /
+    row strides pass without a copy ([B, Nmax, Hkv, 64] memory viewed
+    transposed included). Everything else runs
+    `_attention_ref.kvcache_attention_ref`.
+
+    Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
+    lse [B, H, Nq] fp32."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k_cache, v_cache)):
+        raise RuntimeError('sdpa_kvcache is forward only: call it under torch.no_grad() or detach its inputs')
+    if not _kvcache_usable(q, k_cache, v_cache, kv_len):
+        from ._attention_ref import kvcache_attention_ref
+
+        return kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal, return_lse)
+    B, H, Nq, D = q.shape
+    Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
+    q, k_cache, v_cache = (t if _vector_loadable(t) else t.contiguous() for t in (q, k_cache, v_cache))
+    kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
+    splits = _C.attn_decode_splits(B, Hkv, Nmax, num_splits, q.get_device())
+    o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    # partials of the split kernel; it writes every element the merge reads
+    ws = torch.empty(_C.attn_decode_workspace_floats(B, Hkv, splits), dtype=torch.float32, device=q.device)
+    _C.attn_decode(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits)
+    return (o, lse) if return_lse else o
 
 
 def fused_attention_enabled() -> bool:

@@ -8,6 +8,7 @@ Run:  python examples/gpt2.py
       torchrun --standalone --nproc-per-node 8 examples/gpt2.py
       python examples/gpt2.py --packed    # several documents per row
       python examples/gpt2.py --n-kv-head 4   # grouped-query attention
+      python examples/gpt2.py --sample 16     # 16 greedy tokens after training
 
 --packed fills every row with random-length documents that end in an EOS
 token, keeps attention inside each document (ops.fused_attn: the native
@@ -18,6 +19,10 @@ its own, so its target is the loss's ignore_index.
 --n-kv-head gives K and V that many heads (a divisor of the model's
 n_head; 1 is multi-query attention): the native kernels read the shared
 K/V heads in place and sum each group's dK/dV in registers.
+
+--sample N prints N greedy tokens after training: GPT2.generate prefills
+a K/V cache from an 8-token prompt and decodes through
+ops.fused_attn.sdpa_kvcache (the split-KV decode kernels on the device).
 """
 
 import argparse
@@ -144,12 +149,17 @@ def main():
     parser.add_argument(
         '--n-kv-head', type=int, default=None, help='K/V heads for grouped-query attention (divides n_head)'
     )
+    parser.add_argument('--sample', type=int, default=0, metavar='N', help='print N greedy tokens after training')
     args = parser.parse_args()
 
     init_process_group_auto()
     pipeline = TrainingPipeline(name='gpt2-synthetic')
     pipeline.append_stage(GPT2Stage(packed=args.packed, n_kv_head=args.n_kv_head), max_epochs=MAX_EPOCHS)
     pipeline.run()
+    if args.sample > 0 and torch.distributed.get_rank() == 0:
+        model = pipeline.models['gpt2'].module
+        prompt = torch.arange(1, 9, device=next(model.parameters()).device).unsqueeze(0)
+        print('sampled tokens:', model.generate(prompt, args.sample)[0, 8:].tolist())
 
 
 if __name__ == '__main__':

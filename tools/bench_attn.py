@@ -9,6 +9,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py            # every section
     python tools/bench_attn.py --no-gqa   # the sections before GQA
     python tools/bench_attn.py --gqa      # the GQA section alone
+    python tools/bench_attn.py --decode   # KV-cache decode (sdpa_kvcache) alone
 """
 
 import math
@@ -185,6 +186,49 @@ def bench_gqa(b, h, hkv, n, d=64):
         )
 
 
+HBM_COPY_BYTES_PER_S = 4.4e12  # the copy kernel's measured rate (profiles/ops_bandwidth_mi355x.txt)
+
+
+def bench_decode(b, h, hkv, nmax, d=64):
+    """One causal decode step (Nq = 1) over a FULL cache, kv_len = Nmax:
+    native with the automatic split count | native num_splits=1 | torch
+    SDPA given the boolean [B, 1, 1, Nmax] mask (what a user has today;
+    building the mask is not timed) | the HBM floor: the K + V bytes at the
+    copy kernel's rate."""
+    from dmlcloud_amd.ops.fused_attn import fused_kvcache_usable, sdpa_kvcache
+
+    torch.manual_seed(0)
+    mk = lambda heads, n: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    q, k, v = mk(h, 1), mk(hkv, nmax), mk(hkv, nmax)
+    kv_len = torch.full((b,), nmax, dtype=torch.int32, device=DEV)
+    assert fused_kvcache_usable(q, k, v, kv_len)
+    mask = (torch.arange(nmax, device=DEV)[None, :] < kv_len[:, None]).view(b, 1, 1, nmax)
+    gqa = {'enable_gqa': True} if hkv != h else {}
+    with torch.no_grad():
+        t_auto = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len), reps=200, warmup=20)
+        t_one = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len, num_splits=1), reps=200, warmup=20)
+        t_torch = time_fn(
+            lambda: torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask, **gqa),
+            reps=200,
+            warmup=20,
+        )
+    floor = 2 * k.numel() * k.element_size() / HBM_COPY_BYTES_PER_S * 1e6
+    splits = _C.attn_decode_splits(b, hkv, nmax, 0, 0)
+    print(
+        f'DECODE B={b} H={h} Hkv={hkv} Nmax={nmax}: native S={splits} {t_auto:8.1f}us | native S=1 {t_one:8.1f}us '
+        f'| masked sdpa {t_torch:8.1f}us | HBM floor {floor:6.1f}us ({floor / t_auto:4.2f} of floor reached)'
+    )
+
+
+def main_decode():
+    for rnd in range(3):  # three rounds in one session: the spread
+        print(f'-- round {rnd + 1}')
+        bench_decode(8, 12, 12, 1024)
+        bench_decode(8, 12, 12, 4096)
+        bench_decode(64, 12, 12, 1024)
+        bench_decode(8, 32, 8, 4096)
+
+
 def main_gqa():
     bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
     bench_gqa(64, 12, 1, 1024)  # ... and as MQA
@@ -192,6 +236,9 @@ def main_gqa():
 
 
 if __name__ == '__main__':
+    if '--decode' in sys.argv[1:]:
+        main_decode()
+        sys.exit(0)
     if '--gqa' in sys.argv[1:]:
         main_gqa()
         sys.exit(0)
