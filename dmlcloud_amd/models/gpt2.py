@@ -22,7 +22,9 @@ cache (`init_cache`) from the prompt through the same `sdpa` path as
 training and then decodes one token per `decode_step` through
 ops.fused_attn.sdpa_kvcache, the split-KV decode kernels. The cache
 lengths live on the device and are advanced there, so a step has no host
-sync.
+sync. `GPT2.extend(idx, cache)` appends a whole chunk of tokens to a cache
+that may already hold some (chunked prefill, `generate(prefill_chunk=c)`,
+the next turn of a conversation) through the same op with Nq = T.
 """
 
 import math
@@ -103,6 +105,18 @@ class CausalSelfAttention(nn.Module):
         y = sdpa_kvcache(q, k_cache, v_cache, kv_len, causal=True)
         return self.c_proj(y.transpose(1, 2).reshape(B, 1, C))
 
+    def extend(self, x, k_cache, v_cache, kv_len, batch, rows):
+        """T new tokens per row, x [B, T, C]: their K/V go to cache rows
+        rows[b, t] = kv_len[b] - T + t (one indexed device write per
+        tensor), then token t attends cache rows 0..rows[b, t]."""
+        B, T, C = x.shape
+        q, k, v = self._heads(x)
+        # index result [B, T, n_kv_head, hd]: the layout of k before its transpose
+        k_cache[batch, :, rows] = k.transpose(1, 2)
+        v_cache[batch, :, rows] = v.transpose(1, 2)
+        y = sdpa_kvcache(q, k_cache, v_cache, kv_len, causal=True)
+        return self.c_proj(y.transpose(1, 2).reshape(B, T, C))
+
 
 class Block(nn.Module):
     def __init__(self, cfg: GPT2Config):
@@ -127,6 +141,10 @@ class Block(nn.Module):
 
     def decode(self, x, *cache_args):
         x = x + self.attn.decode(self.ln_1(x), *cache_args)
+        return x + self.mlp(self.ln_2(x))
+
+    def extend(self, x, *cache_args):
+        x = x + self.attn.extend(self.ln_1(x), *cache_args)
         return x + self.mlp(self.ln_2(x))
 
 
@@ -229,15 +247,40 @@ class GPT2(nn.Module):
         return self.lm_head(self.ln_f(x[:, 0]))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None):
+    def extend(self, idx, cache: KVCache):
+        """Append idx [B, T] to a cache that may already hold tokens (each
+        row its own count) and return the last position's logits
+        [B, vocab]: chunked prefill, or the next turn of a conversation.
+        Positions and cache rows come from cache.kv_len on the device;
+        nothing is read back. Attention runs through sdpa_kvcache with
+        Nq = T."""
+        B, T = idx.shape
+        rows = cache.kv_len.long().unsqueeze(1) + torch.arange(T, device=idx.device)  # [B, T], before the increment
+        cache.kv_len += T
+        batch = torch.arange(B, device=idx.device).unsqueeze(1)
+        x = self.wte(idx) + self.wpe(rows.clamp(max=self.cfg.n_positions - 1))
+        for block, k_cache, v_cache in zip(self.blocks, cache.k, cache.v):
+            # (a full cache overwrites its last row instead of writing past it)
+            x = block.extend(x, k_cache, v_cache, cache.kv_len, batch, rows.clamp(max=k_cache.shape[2] - 1))
+        return self.lm_head(self.ln_f(x[:, -1]))
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None, prefill_chunk=None):
         """idx [B, T] followed by max_new_tokens sampled tokens,
         [B, T + max_new_tokens]. temperature = 0 is greedy; otherwise the
-        next token is drawn from softmax(logits / temperature)."""
+        next token is drawn from softmax(logits / temperature). The prompt
+        runs through `prefill` in one piece, or with prefill_chunk = c >= 1
+        through `extend` in pieces of at most c tokens."""
         B, T = idx.shape
         assert T >= 1 and T + max_new_tokens <= self.cfg.n_positions, 'sequence exceeds n_positions'
         cache = self.init_cache(B, T + max_new_tokens)
         out = [idx]
-        logits = self.prefill(idx, cache)
+        if prefill_chunk is None:
+            logits = self.prefill(idx, cache)
+        else:
+            assert prefill_chunk >= 1, 'prefill_chunk must be >= 1'
+            for piece in idx.split(prefill_chunk, dim=1):
+                logits = self.extend(piece, cache)
         for step in range(max_new_tokens):
             if step > 0:
                 logits = self.decode_step(out[-1].view(B), cache)

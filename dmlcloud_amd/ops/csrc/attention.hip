@@ -11,6 +11,10 @@
 //   attn_decode_split_kernel / attn_decode_merge_kernel: a few new q rows
 //                         over a K/V cache with device-resident lengths,
 //                         keys split over blocks (see "KV-cache decode").
+//   attn_decode_tiled_kernel / attn_decode_tiled_merge_kernel: the same for
+//                         more than 16 query columns per K/V head, up to four
+//                         16-column tiles per block (see "KV-cache, more than
+//                         16 columns").
 // Fragment maps of v_mfma_f32_16x16x32_bf16, empirically confirmed
 // (profiles/mfma_16x16x32_bf16_layout.txt):
 //   A (bf16x8): lane l elem j <-> A[l%16][8*(l/16)+j]
@@ -1476,6 +1480,400 @@ void attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at
                        stream, (const float*)ws_o, (const float*)ws_ml, kv_len.data_ptr<int>(),
                        (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(), (int)H, (int)G, (int)Nq,
                        (int)Nmax, S, chunk, causal);
+  }
+}
+
+// ===========================================================================
+// KV-cache, more than 16 columns: tiled split-KV forward + merge
+// ===========================================================================
+//
+// The same contract as the decode kernels above (decode_len, positions, no
+// read at or past len, no atomics) for ANY R = G * Nq >= 1: chunked prefill,
+// speculative verification, wide GQA groups. The work split:
+//   * the R columns c = g * Nq + i of one K/V head are cut into
+//     nt = ceil(R / 16) MFMA column tiles; tile t owns columns 16t..16t+15,
+//     columns >= R re-read column R - 1 and are never stored;
+//   * a block serves one (b, K/V head, tile GROUP, split); a group is up to
+//     kTileGroup = 4 consecutive tiles of which `live` exist;
+//   * the four waves take ROLES from live: T = 1, 2 or 4 column tiles side by
+//     side (three live tiles run as T = 4 with one role idle). Wave w owns
+//     column tile w % T of the group and key phase w / T of P = 4 / T, and
+//     walks the 32-key tiles k_begin + 32 * (phase + P * t) of the split on
+//     its own: T = 1 is the decode kernel's split, T = 4 makes every wave
+//     walk all keys of the split for its own 16 columns. The T waves that
+//     share a key tile read it through L1/L2, not through LDS;
+//   * the per-tile code is the decode kernel's (K as global A fragments, V
+//     through the wave's two images, P through the wave's slice, the next
+//     tile's loads under the current math, every key row clamped to len - 1,
+//     one compare per score); the roles are wave-uniform run-time integers;
+//   * causal skip: a wave passes over key tiles beyond the largest key any of
+//     its columns attends (lim_max below);
+//   * the waves' (m, l, O) meet in LDS behind one barrier; for each live tile
+//     its P phase partials are combined in ascending phase. S == 1 stores,
+//     S > 1 writes one partial per (tile, split) to the workspace,
+//     O [B, Hkv, nt, S, 16, 64] then (m, l) [B, Hkv, nt, S, 16, 2], and
+//     attn_decode_tiled_merge_kernel combines the live splits in ascending
+//     order.
+constexpr int kTileGroup = kWavesPerBlock; // column tiles of one block, at most
+
+// amdgpu_waves_per_eu(4): the block's LDS admits four blocks per CU, the
+// decode kernel's occupancy; left alone the allocator takes 130 registers,
+// two more than four waves per SIMD allow.
+kDecodeFn __global__ void __launch_bounds__(kAttnThreads) __attribute__((amdgpu_waves_per_eu(4)))
+attn_decode_tiled_kernel(
+    const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
+    const __hip_bfloat16* __restrict__ v, const int* __restrict__ kv_len,
+    __hip_bfloat16* __restrict__ o, float* __restrict__ lse, float* __restrict__ ws_o,
+    float* __restrict__ ws_ml, int H, int G, int Nq, int Nmax, int S, int chunk, float scale,
+    bool causal, Strides sq, Strides sk, Strides sv) {
+  __shared__ DecodeWaveLds wave_lds[kWavesPerBlock];
+  __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStride];
+
+  const Coords tc = thread_coords();
+  const int lane = tc.lane, row16 = tc.row16, grp = tc.grp, st_col = tc.st_col;
+  const int wave = __builtin_amdgcn_readfirstlane(tc.wave);
+  __hip_bfloat16(*p_lds)[kPStride] = p_lds_all[wave];
+  const __hip_bfloat16* v_img = (const __hip_bfloat16*)wave_lds[wave].v[0];
+  const int st_row = lane >> 3; // the WAVE stages a 32x64 V tile, as in decode
+
+  // grid: (b, K/V head, tile group, split), split fastest
+  const int Hkv = H / G;
+  const int R = G * Nq;
+  const int nt = (R + kDecCols - 1) / kDecCols;
+  const int groups = (nt + kTileGroup - 1) / kTileGroup;
+  const int s = blockIdx.x % S;
+  const int tg = (blockIdx.x / S) % groups;
+  const int kvh = (blockIdx.x / S / groups) % Hkv;
+  const int b = blockIdx.x / S / groups / Hkv;
+  const int len = decode_len(kv_len, b, Nq, Nmax, causal);
+
+  // roles
+  const int live = min(kTileGroup, nt - tg * kTileGroup); // 1..4
+  const int T = live == 1 ? 1 : live == 2 ? 2 : 4;
+  const int P = kWavesPerBlock / T;
+  const int tile_in_group = wave % T, phase = wave / T;
+  const int tile = tg * kTileGroup + tile_in_group; // >= nt: the idle role of live == 3
+
+  // Which keys are walked, per (column tile, phase) now. Split s owns keys
+  // [s * chunk, (s + 1) * chunk), S * chunk >= Nmax >= len (launcher); a
+  // split with k_begin >= len returns before the barrier, all threads alike,
+  // and the merge kernel derives the same live count from the same len.
+  // lim_max is the largest key any column of the wave's tile attends:
+  // len - 1 when not causal or when the tile holds a column with i = Nq - 1
+  // (a multiple of Nq in (c0, c1 + 1]: every tile that crosses a head
+  // boundary, and the last tile, whose c1 + 1 = R = G * Nq), else the
+  // position of its last column, the largest i of the tile. The wave walks
+  // key0 = k_begin + 32 * (phase + P * t) < k_stop = min(k_begin + chunk,
+  // lim_max + 1) <= len (wave-uniform).
+  // Every stored column meets each of its keys exactly once: a key j <= lim
+  // of a column of tile ct lies in the one split s = j / chunk (live:
+  // k_begin <= j < len), there in the one 32-key tile key0 = j -
+  // (j - k_begin) % 32, which belongs to the one phase ((key0 - k_begin) /
+  // 32) % P of the one wave that owns (ct, phase); key0 <= j <= lim <=
+  // lim_max and key0 < k_begin + chunk, so that wave walks it. Keys > lim
+  // in a walked tile score -1e30 (the compare), rows >= len are never
+  // loaded (the clamp). Key 0 is attended by every stored column (p >= 0)
+  // and sits in split 0, phase 0, t = 0 with lim_max >= 0, so a stored
+  // column's merged maximum is a real score and its l >= exp2(0).
+  // The wipe: a column that meets only masked keys in a wave's walk keeps
+  // m = -1e30 with alpha = 1 and p = 1: finite garbage in l and O (real V
+  // rows < len), which exp2(-1e30 - M) = 0 removes wherever it meets a real
+  // maximum M: another phase (block epilogue) or another split (merge). A
+  // wave that walks nothing (skipped by lim_max, no tile left for its phase,
+  // or the idle role) leaves the empty partial m = -1e30, l = 0, O = 0.
+  const int k_begin = s * chunk;
+  if (k_begin >= len) return;
+  const int c0 = tile * kDecCols, c1 = min(c0 + kDecCols - 1, R - 1);
+  int lim_max = len - 1;
+  if (causal && (c1 + 1) / Nq == c0 / Nq) lim_max = len - Nq + (c1 - c0 / Nq * Nq);
+  const int k_stop = tile < nt ? min(k_begin + chunk, lim_max + 1) : k_begin;
+
+  // this lane's query column: Q B-fragments, and the last key it attends
+  const int col_q = min(c0 + row16, R - 1);
+  const int g_q = col_q / Nq;
+  const int i_q = col_q - g_q * Nq;
+  const int lim = causal ? len - Nq + i_q : len - 1;
+  const __hip_bfloat16* qp = q + (int64_t)b * sq.b + (int64_t)(kvh * G + g_q) * sq.h + (int64_t)i_q * sq.r;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) qf[c] = *(const bf16x8*)(qp + 32 * c + 8 * grp);
+
+  const __hip_bfloat16* kp = k + (int64_t)b * sk.b + (int64_t)kvh * sk.h;
+  const __hip_bfloat16* vp = v + (int64_t)b * sv.b + (int64_t)kvh * sv.h;
+  // K fragments [16-key half h][k-chunk c] and V pieces of the tile at key0,
+  // every row clamped to len - 1; K before V, pinned (see the decode kernel)
+  auto load_tile = [&](int key0, bf16x8(&kf)[2][2], bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t kr = min(key0 + 16 * h + row16, len - 1);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) kf[h][c] = *(const bf16x8*)(kp + kr * sk.r + 32 * c + 8 * grp);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int64_t vr = min(key0 + st_row + 8 * x, len - 1);
+      vpc[x] = *(const bf16x8*)(vp + vr * sv.r + st_col);
+    }
+  };
+  auto stage_v = [&](int buf, const bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      *(bf16x8*)(&wave_lds[wave].v[buf][vt_idx(st_row + 8 * x, st_col)]) = vpc[x];
+    }
+  };
+
+  const float scale2 = scale * kLog2e;
+  float m_run = -1e30f, l_run = 0.0f;
+  f32x4 o_acc[4];
+#pragma unroll
+  for (int db = 0; db < 4; ++db) o_acc[db] = f32x4{0, 0, 0, 0};
+
+  const int key_step = P * kKT;
+  int key0 = k_begin + phase * kKT;
+  bool have = key0 < k_stop;
+  bf16x8 kf[2][2], vpc[4];
+  if (have) {
+    load_tile(key0, kf, vpc);
+    stage_v(0, vpc);
+  }
+  int buf = 0;
+  while (have) {
+    // the next tile's loads stay in flight through this tile's math
+    const int key_next = key0 + key_step;
+    const bool has_next = key_next < k_stop;
+    bf16x8 kf_next[2][2];
+    if (has_next) load_tile(key_next, kf_next, vpc);
+
+    // ---- S^T = K Q^T: rows = key (16h + 4grp + r), col = row16 ----
+    float sc[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[h][c], qf[c], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = acc[r] * scale2;
+        // one compare against the lane's OWN lim: causal end, cache end and
+        // clamped duplicates alike
+        if (key0 + 16 * h + 4 * grp + r > lim) x = -1e30f;
+        sc[4 * h + r] = x;
+      }
+    }
+
+    // ---- online softmax (per column row16; reduce across the grp groups) ----
+    float mt = sc[0];
+#pragma unroll
+    for (int x = 1; x < 8; ++x) mt = fmaxf(mt, sc[x]);
+    mt = fmaxf(mt, decode_shfl(mt, lane ^ 16));
+    mt = fmaxf(mt, decode_shfl(mt, lane ^ 32));
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    float ps = 0.0f;
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+      sc[x] = __builtin_amdgcn_exp2f(sc[x] - m_new);
+      ps += sc[x];
+    }
+    ps += decode_shfl(ps, lane ^ 16);
+    ps += decode_shfl(ps, lane ^ 32);
+    l_run = l_run * alpha + ps;
+    m_run = m_new;
+
+    // ---- P^T -> the wave's LDS slice, back as the A operand ----
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      bf16x4 pw;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pw[r] = (__bf16)sc[4 * h + r];
+      *(bf16x4*)(&p_lds[row16][16 * h + 4 * grp]) = pw;
+    }
+    float a_o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a_o[r] = decode_shfl(alpha, 4 * grp + r);
+    const bf16x8 pf = *(const bf16x8*)(&p_lds[row16][8 * grp]);
+
+    // ---- O = alpha O + P V: rows = column (4grp + r), cols = 16db + row16 ----
+#pragma unroll
+    for (int db = 0; db < 4; ++db) {
+      const bf16x8 vf = read_tr_frag(v_img + buf * kImgElems, db, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o_acc[db][r] *= a_o[r];
+      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, o_acc[db], 0, 0, 0);
+    }
+
+    if (has_next) {
+      stage_v(buf ^ 1, vpc); // the image this tile did not read
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) kf[h][c] = kf_next[h][c];
+    }
+    key0 = key_next;
+    buf ^= 1;
+    have = has_next;
+  }
+
+  // ---- block epilogue: the waves' (m, l, O) through LDS, one barrier ----
+  // (a wave overwrites its OWN images, after its own last read of them)
+#pragma unroll
+  for (int db = 0; db < 4; ++db) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wave_lds[wave].part.o[4 * grp + r][16 * db + row16] = o_acc[db][r];
+  }
+  if (lane < kDecCols) {
+    wave_lds[wave].part.ml[row16][0] = m_run;
+    wave_lds[wave].part.ml[row16][1] = l_run;
+  }
+  decode_barrier();
+
+  // tile t of the group: the partials of waves t, t + T, ... in ascending phase
+  const int col = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+  for (int t = 0; t < live; ++t) {
+    const DecodeAcc a = decode_combine(&wave_lds[t].part.o[0][0], &wave_lds[t].part.ml[0][0], P,
+                                       T * kDecWaveLdsFloats, T * kDecWaveLdsFloats, col, d4);
+    const int gt = tg * kTileGroup + t; // < nt
+    if (S == 1) {
+      const int c = gt * kDecCols + col;
+      if (c < R) decode_store(a, o, lse, b, kvh, H, G, Nq, c, d4);
+    } else {
+      // all 16 columns: the duplicates of column R - 1 are finite and unread
+      const int64_t part = (((int64_t)b * Hkv + kvh) * nt + gt) * S + s;
+      *(f32x4*)(ws_o + part * kDecPartO + col * kAttnD + d4) = a.o;
+      if (d4 == 0) {
+        ws_ml[part * kDecPartML + 2 * col] = a.m;
+        ws_ml[part * kDecPartML + 2 * col + 1] = a.l;
+      }
+    }
+  }
+}
+
+// One block per (b, K/V head, tile group): for every live tile, combine the
+// partials of the splits that ran, 0..n_live-1 (split s ran iff
+// s * chunk < len, the split kernel's early return), and store the columns
+// < R. Nothing else of the (uninitialised) workspace is read.
+kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_tiled_merge_kernel(
+    const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
+    const int* __restrict__ kv_len, __hip_bfloat16* __restrict__ o, float* __restrict__ lse,
+    int H, int G, int Nq, int Nmax, int S, int chunk, bool causal) {
+  const int Hkv = H / G;
+  const int R = G * Nq;
+  const int nt = (R + kDecCols - 1) / kDecCols;
+  const int groups = (nt + kTileGroup - 1) / kTileGroup;
+  const int tg = blockIdx.x % groups;
+  const int kvh = (blockIdx.x / groups) % Hkv;
+  const int b = blockIdx.x / groups / Hkv;
+  const int len = decode_len(kv_len, b, Nq, Nmax, causal);
+  const int n_live = min(S, (len + chunk - 1) / chunk); // >= 1: len >= 1
+  const int col = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+  const int live = min(kTileGroup, nt - tg * kTileGroup);
+  for (int t = 0; t < live; ++t) {
+    const int gt = tg * kTileGroup + t;
+    const int c = gt * kDecCols + col;
+    if (c >= R) continue;
+    const int64_t part = (((int64_t)b * Hkv + kvh) * nt + gt) * S;
+    const DecodeAcc a = decode_combine(ws_o + part * kDecPartO, ws_ml + part * kDecPartML, n_live,
+                                       kDecPartO, kDecPartML, col, d4);
+    decode_store(a, o, lse, b, kvh, H, G, Nq, c, d4);
+  }
+}
+
+static int64_t tiled_tiles(int64_t R) { return ceil_div(R, kDecCols); }
+static int64_t tiled_groups(int64_t R) { return ceil_div(tiled_tiles(R), kTileGroup); }
+
+int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S) {
+  // one partial per (b, K/V head, column tile, split); S == 1 stores directly
+  return S > 1 ? B * Hkv * tiled_tiles(R) * S * (kDecPartO + kDecPartML) : 0;
+}
+
+// The split count a call runs with: `num_splits` when positive, else
+// S = clamp(ceil(2 * CUs / (B * Hkv * groups)), 1, ceil(Nmax / 128)): about
+// two blocks per CU. Shapes and the device only, never kv_len, so a captured
+// call keeps its grid. The factor 2 is inherited from attn_decode_splits and
+// is as unmeasured here as it is there.
+int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax,
+                                 int64_t num_splits, int64_t device) {
+  TORCH_CHECK(B >= 1 && Hkv >= 1 && R >= 1 && Nmax >= 1,
+              "attn_decode_tiled: B, Hkv, R and Nmax must be >= 1");
+  const int64_t max_splits = ceil_div(Nmax, kDecChunkAlign);
+  TORCH_CHECK(num_splits >= 0 && num_splits <= max_splits, "num_splits must lie in [0, ceil(Nmax / ",
+              kDecChunkAlign, ")] = [0, ", max_splits, "], got ", num_splits);
+  if (num_splits > 0) return num_splits;
+  int cus = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, (int)device) ==
+                      hipSuccess && cus > 0,
+              "attn_decode_tiled: cannot read the CU count of device ", device);
+  TORCH_CHECK(B * Hkv <= INT32_MAX && tiled_groups(R) <= INT32_MAX, "attn_decode_tiled: too many blocks");
+  return std::min(std::max<int64_t>(ceil_div(2 * (int64_t)cus, B * Hkv * tiled_groups(R)), 1),
+                  max_splits);
+}
+
+void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
+                       at::Tensor lse, at::Tensor ws, double scale, bool causal,
+                       int64_t num_splits) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1 &&
+                  q.size(0) >= 1 && q.scalar_type() == at::kBFloat16,
+              "q must be a bf16 device tensor [B,H,Nq,64] with B, Nq >= 1 (head dim 64 only)");
+  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2);
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == kAttnD && k.size(1) >= 1 &&
+                  H % k.size(1) == 0 && H >= 1,
+              "k_cache must be [B,Hkv,Nmax,64] with q's B and a head count Hkv that divides q's: "
+              "got ", k.sizes(), " for q ", q.sizes());
+  const int64_t Hkv = k.size(1), Nmax = k.size(2), G = H / Hkv;
+  TORCH_CHECK(v.sizes() == k.sizes(), "v_cache must be shaped like k_cache");
+  TORCH_CHECK(Nmax >= Nq, "the cache must hold the Nq new rows: Nmax ", Nmax, " < Nq ", Nq);
+  TORCH_CHECK(Nmax <= INT32_MAX - 2 * kDecChunkAlign && B * H * Nq <= INT32_MAX / kAttnD,
+              "attn_decode_tiled: Nmax or B*H*Nq too large");
+  const int64_t R = G * Nq;
+  for (const NamedTensor& a : {NamedTensor{"q", q}, {"k_cache", k}, {"v_cache", v}}) {
+    const at::Tensor& t = a.second;
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.device() == q.device() && t.stride(3) == 1,
+                a.first, " must be bf16 on q's device with a contiguous last dim");
+    // rows are read as 16-byte vectors
+    TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0 && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 &&
+                    t.stride(2) % 8 == 0,
+                a.first, " must be 16-byte aligned with batch/head/row strides that are multiples "
+                         "of 8 elements");
+  }
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.device() == q.device() &&
+                  kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              "kv_len must be int32 [B], contiguous, on q's device");
+  TORCH_CHECK(o.scalar_type() == at::kBFloat16 && o.device() == q.device() &&
+                  o.sizes() == q.sizes() && o.is_contiguous(),
+              "o must be bf16, shaped like q, contiguous, on q's device");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.device() == q.device() &&
+                  lse.numel() == B * H * Nq && lse.is_contiguous(),
+              "lse must be fp32 [B,H,Nq], contiguous, on q's device");
+  const int64_t S = attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device());
+  const int64_t ws_floats = attn_decode_tiled_workspace_floats(B, Hkv, R, S);
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.device() == q.device() && ws.is_contiguous() &&
+                  ws.numel() >= ws_floats && (ws.numel() == 0 || (uintptr_t)ws.data_ptr() % 16 == 0),
+              "the workspace must be fp32, contiguous, 16-byte aligned, on q's device, with >= ",
+              ws_floats, " elements for ", S, " splits of ", tiled_tiles(R), " column tiles");
+  const int64_t groups = tiled_groups(R);
+  // chunk: ceil(Nmax / S) rounded up to whole 128-key rounds, so S * chunk >= Nmax
+  const int64_t chunk = ceil_div(ceil_div(Nmax, S), kDecChunkAlign) * kDecChunkAlign;
+  TORCH_CHECK(B * Hkv * groups * S <= INT32_MAX && S * chunk <= INT32_MAX,
+              "attn_decode_tiled: too many blocks or keys");
+
+  auto stream = c10::hip::getCurrentHIPStream();
+  float* ws_o = S > 1 ? ws.data_ptr<float>() : nullptr;
+  float* ws_ml = S > 1 ? ws_o + B * Hkv * tiled_tiles(R) * S * kDecPartO : nullptr;
+  hipLaunchKernelGGL(attn_decode_tiled_kernel, dim3((unsigned)(B * Hkv * groups * S)),
+                     dim3(kAttnThreads), 0, stream, (const __hip_bfloat16*)q.data_ptr(),
+                     (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
+                     kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(),
+                     ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax, (int)S, (int)chunk,
+                     (float)scale, causal, strides_of(q), strides_of(k), strides_of(v));
+  if (S > 1) {
+    hipLaunchKernelGGL(attn_decode_tiled_merge_kernel, dim3((unsigned)(B * Hkv * groups)),
+                       dim3(kAttnThreads), 0, stream, (const float*)ws_o, (const float*)ws_ml,
+                       kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(),
+                       lse.data_ptr<float>(), (int)H, (int)G, (int)Nq, (int)Nmax, (int)S,
+                       (int)chunk, causal);
   }
 }
 

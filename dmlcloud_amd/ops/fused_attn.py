@@ -37,12 +37,15 @@ whenever the native path is not usable, the same mask is handed to
 torch SDPA as a boolean attn_mask. Verified in
 tests/test_gpu_attention_docmask.py.
 
-Decoding: `sdpa_kvcache(q, k_cache, v_cache, kv_len)` attends a few new
-query rows to a partly filled [B, Hkv, Nmax, 64] K/V cache whose per-row
-lengths live on the device. It has kernels of its own (split-KV decode
-plus a merge pass, ops/csrc/attention.hip) and never goes through `sdpa`,
+Decoding: `sdpa_kvcache(q, k_cache, v_cache, kv_len)` attends new query
+rows (one token, a few draft tokens, a chunk of a prompt) to a partly
+filled [B, Hkv, Nmax, 64] K/V cache whose per-row lengths live on the
+device. It has kernels of its own (split-KV decode plus a merge pass, and
+their tiled form for more than 16 query columns per K/V head,
+ops/csrc/attention.hip) and never goes through `sdpa`,
 whose behaviour for kv length != q length (torch SDPA, top-left causal)
-is unchanged. Verified in tests/test_gpu_attention_kvcache.py.
+is unchanged. Verified in tests/test_gpu_attention_kvcache.py and
+tests/test_gpu_attention_kvcache_tiled.py.
 """
 
 import math
@@ -251,7 +254,7 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len):
         and k_cache.shape[3] == 64
         and k_cache.shape[1] >= 1
         and q.shape[1] % k_cache.shape[1] == 0
-        and 1 <= (q.shape[1] // k_cache.shape[1]) * q.shape[2] <= 16
+        and (q.shape[1] // k_cache.shape[1]) * q.shape[2] >= 1
         and k_cache.shape[2] >= q.shape[2]
         and v_cache.shape == k_cache.shape
         and k_cache.dtype == q.dtype
@@ -267,10 +270,10 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len):
 
 def fused_kvcache_usable(q, k_cache, v_cache, kv_len) -> bool:
     """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len)` will run the
-    native split-KV decode kernels, False when it will run the pure-torch
-    reference: bf16 device tensors, q [B, H, Nq, 64], caches
-    [B, Hkv, Nmax, 64] with Hkv dividing H, 1 <= (H / Hkv) * Nq <= 16,
-    Nmax >= Nq, last dims contiguous, an integer [B] kv_len on q's device,
+    native split-KV kernels, False when it will run the pure-torch
+    reference: bf16 device tensors, q [B, H, Nq, 64] with any Nq >= 1,
+    caches [B, Hkv, Nmax, 64] with Hkv dividing H, Nmax >= Nq, last dims
+    contiguous, an integer [B] kv_len on q's device,
     extension built, no DMLCLOUD_DISABLE_FUSED_ATTN."""
     return bool(_kvcache_usable(q, k_cache, v_cache, kv_len))
 
@@ -281,8 +284,9 @@ def _vector_loadable(t):
 
 
 def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: int = 0, return_lse: bool = False):
-    """Attention of a few new query rows over a partly filled K/V cache
-    (decoding); forward only.
+    """Attention of new query rows over a partly filled K/V cache: one row
+    (decoding), a few (speculative verification) or a whole chunk of a
+    prompt (chunked prefill, continuation); forward only.
 
     q is [B, H, Nq, D]; k_cache and v_cache are [B, Hkv, Nmax, D] with Hkv
     dividing H (query head h reads K/V head h // (H // Hkv), as in `sdpa`);
@@ -300,8 +304,11 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     `num_splits` blocks per (b, K/V head), 0 = chosen from the shapes and
     the device's CU count, and merged by a second kernel; any batch / head /
     row strides pass without a copy ([B, Nmax, Hkv, 64] memory viewed
-    transposed included). Everything else runs
-    `_attention_ref.kvcache_attention_ref`.
+    transposed included). R = (H / Hkv) * Nq query columns share a K/V
+    head: R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16 the
+    tiled ones (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four per
+    block, key tiles past a tile's last causal position skipped). Everything
+    else runs `_attention_ref.kvcache_attention_ref`.
 
     Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
     lse [B, H, Nq] fp32."""
@@ -315,6 +322,15 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
     q, k_cache, v_cache = (t if _vector_loadable(t) else t.contiguous() for t in (q, k_cache, v_cache))
     kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
+    R = (H // Hkv) * Nq
+    if R > 16:
+        splits = _C.attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device())
+        o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
+        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+        # one partial per (column tile, split); every element the merge reads is written
+        ws = torch.empty(_C.attn_decode_tiled_workspace_floats(B, Hkv, R, splits), dtype=torch.float32, device=q.device)
+        _C.attn_decode_tiled(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits)
+        return (o, lse) if return_lse else o
     splits = _C.attn_decode_splits(B, Hkv, Nmax, num_splits, q.get_device())
     o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)

@@ -23,6 +23,9 @@ K/V heads in place and sum each group's dK/dV in registers.
 --sample N prints N greedy tokens after training: GPT2.generate prefills
 a K/V cache from an 8-token prompt and decodes through
 ops.fused_attn.sdpa_kvcache (the split-KV decode kernels on the device).
+--prefill-chunk C feeds that prompt to the cache C tokens at a time through
+GPT2.extend instead (the tiled KV-cache kernels once a chunk has more than
+16 query columns per K/V head).
 """
 
 import argparse
@@ -150,6 +153,9 @@ def main():
         '--n-kv-head', type=int, default=None, help='K/V heads for grouped-query attention (divides n_head)'
     )
     parser.add_argument('--sample', type=int, default=0, metavar='N', help='print N greedy tokens after training')
+    parser.add_argument(
+        '--prefill-chunk', type=int, default=None, metavar='C', help='with --sample: prefill the prompt C tokens at a time'
+    )
     args = parser.parse_args()
 
     init_process_group_auto()
@@ -159,7 +165,8 @@ def main():
     if args.sample > 0 and torch.distributed.get_rank() == 0:
         model = pipeline.models['gpt2'].module
         prompt = torch.arange(1, 9, device=next(model.parameters()).device).unsqueeze(0)
-        print('sampled tokens:', model.generate(prompt, args.sample)[0, 8:].tolist())
+        out = model.generate(prompt, args.sample, prefill_chunk=args.prefill_chunk)
+        print('sampled tokens:', out[0, 8:].tolist())
 
 
 if __name__ == '__main__':

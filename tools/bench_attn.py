@@ -10,6 +10,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py --no-gqa   # the sections before GQA
     python tools/bench_attn.py --gqa      # the GQA section alone
     python tools/bench_attn.py --decode   # KV-cache decode (sdpa_kvcache) alone
+    python tools/bench_attn.py --decode-tiled   # sdpa_kvcache, more than 16 columns
 """
 
 import math
@@ -229,6 +230,48 @@ def main_decode():
         bench_decode(8, 32, 8, 4096)
 
 
+def bench_decode_tiled(b, h, hkv, nq, nmax, d=64):
+    """Nq new causal rows with (H / Hkv) * Nq > 16 over a FULL cache,
+    kv_len = Nmax: native tiled kernels with the automatic split count |
+    native num_splits=1 | kvcache_attention_ref on the device (what
+    sdpa_kvcache ran for these shapes before the tiled kernels) | for
+    Nq >= 64, the training forward sdpa() over the chunk's own Nq keys alone:
+    fewer FLOPs, but the project's compute-bound rate."""
+    from dmlcloud_amd.ops._attention_ref import kvcache_attention_ref
+    from dmlcloud_amd.ops.fused_attn import fused_kvcache_usable, sdpa, sdpa_kvcache
+
+    torch.manual_seed(0)
+    mk = lambda heads, n: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    q, k, v = mk(h, nq), mk(hkv, nmax), mk(hkv, nmax)
+    kv_len = torch.full((b,), nmax, dtype=torch.int32, device=DEV)
+    r = h // hkv * nq
+    assert r > 16 and fused_kvcache_usable(q, k, v, kv_len)
+    with torch.no_grad():
+        t_auto = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len), reps=200, warmup=20)
+        t_one = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len, num_splits=1), reps=200, warmup=20)
+        t_ref = time_fn(lambda: kvcache_attention_ref(q, k, v, kv_len, True, False), reps=200, warmup=20)
+        line = ''
+        if nq >= 64:
+            t_fwd = time_fn(lambda: sdpa(q, k[:, :, -nq:], v[:, :, -nq:], causal=True), reps=200, warmup=20)
+            line = f' | sdpa over the chunk alone {t_fwd:8.1f}us ({2 * b * h * nq * nq * d / t_fwd / 1e6:6.1f} TF)'
+    # causal, full cache: row i attends nmax - nq + i + 1 keys
+    flops = 4 * b * h * d * (nq * (nmax - nq) + nq * (nq + 1) / 2)
+    splits = _C.attn_decode_tiled_splits(b, hkv, r, nmax, 0, 0)
+    print(
+        f'DECODE-TILED B={b} H={h} Hkv={hkv} Nq={nq} Nmax={nmax} R={r}: native S={splits} {t_auto:8.1f}us '
+        f'({flops / t_auto / 1e6:6.1f} TF) | native S=1 {t_one:8.1f}us | torch reference {t_ref:8.1f}us' + line
+    )
+
+
+def main_decode_tiled():
+    for rnd in range(3):  # three rounds in one session: the spread
+        print(f'-- round {rnd + 1}')
+        bench_decode_tiled(8, 12, 12, 32, 1024)
+        bench_decode_tiled(8, 32, 4, 4, 4096)
+        bench_decode_tiled(8, 12, 12, 256, 1024)
+        bench_decode_tiled(1, 12, 12, 512, 4096)
+
+
 def main_gqa():
     bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
     bench_gqa(64, 12, 1, 1024)  # ... and as MQA
@@ -238,6 +281,9 @@ def main_gqa():
 if __name__ == '__main__':
     if '--decode' in sys.argv[1:]:
         main_decode()
+        sys.exit(0)
+    if '--decode-tiled' in sys.argv[1:]:
+        main_decode_tiled()
         sys.exit(0)
     if '--gqa' in sys.argv[1:]:
         main_gqa()
