@@ -3,7 +3,7 @@
 Self-contained GPT-2 (124M): learned positional embeddings, pre-LN
 blocks, GELU MLP, tied LM head. Attention goes through
 ops.fused_attn.sdpa: the project's MFMA flash-attention kernels for bf16
-device tensors with head dim 64 (GPT-2 small), torch SDPA otherwise.
+device tensors with head dim 64 (GPT-2 small) or 128, torch SDPA otherwise.
 
 Packed sequences: `GPT2.forward(idx, targets, doc_ids=...)` takes an
 integer [B, T] tensor whose runs of equal values are the documents packed
@@ -71,7 +71,7 @@ class CausalSelfAttention(nn.Module):
         q = q.view(B, T, self.n_head, C // self.n_head).transpose(1, 2)
         k = k.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
         v = v.view(B, T, self.n_kv_head, C // self.n_head).transpose(1, 2)
-        # custom MFMA flash attention on bf16/D=64 (ops/fused_attn.py);
+        # custom MFMA flash attention on bf16, D = 64 or 128 (ops/fused_attn.py);
         # beats AOTriton fwd+bwd combined at this shape — falls back to
         # torch SDPA otherwise
         y = sdpa(q, k, v, causal=True) if doc_start is None else sdpa(q, k, v, causal=True, doc_start=doc_start)

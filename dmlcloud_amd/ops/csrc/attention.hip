@@ -1,4 +1,5 @@
-// Flash attention for gfx950: forward and backward, MFMA bf16, head dim 64,
+// Flash attention for gfx950: forward and backward, MFMA bf16, head dim 64
+// (this file) and 128 (attention_d128.h, included at the end),
 // self-attention geometry, any N >= 1, optional packed documents. Tiling
 // mirrors ops/_attention_ref.py exactly. A block is 4 waves of one (b, h):
 //   attn_fwd_kernel       wave owns 32 q rows (two 16-row sub-tiles), block
@@ -545,24 +546,27 @@ static int attn_grid(int BH, int N, int rows_per_block) {
 }
 
 // Everything both launchers require of their tensors, before any launch.
-// q is [B, H, N, 64]; k is [B, Hkv, N, 64] with 1 <= Hkv <= H and H % Hkv == 0
-// (Hkv < H is grouped-query attention). `strided`: bf16 on q's device, last
-// dim contiguous (reached through per-tensor strides), `like_q` shaped like q
-// and `like_k` shaped like k. `dense`: the same, but indexed as contiguous
-// [B*heads, N, 64]. `row_stats` (lse, delta): fp32 on q's device, >= B*H*N
-// elements. Returns the group size G = H / Hkv.
+// q is [B, H, N, D], D = 64 or 128; k is [B, Hkv, N, D] with 1 <= Hkv <= H and
+// H % Hkv == 0 (Hkv < H is grouped-query attention). `strided`: bf16 on q's
+// device, last dim contiguous (reached through per-tensor strides), `like_q`
+// shaped like q and `like_k` shaped like k, so every tensor has q's D.
+// `dense`: the same, but indexed as contiguous [B*heads, N, D]. `row_stats`
+// (lse, delta): fp32 on q's device, >= B*H*N elements. Returns the group size
+// G = H / Hkv.
 using NamedTensor = std::pair<const char*, const at::Tensor&>;
 using NamedTensors = std::initializer_list<NamedTensor>;
 static int check_attn_args(const at::Tensor& q, const at::Tensor& k, NamedTensors strided_like_q,
                            NamedTensors strided_like_k, NamedTensors dense_like_q,
                            NamedTensors dense_like_k, NamedTensors row_stats) {
-  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1,
-              "q must be a device tensor [B,H,N,64] with N >= 1 (head dim 64 only)");
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && (q.size(3) == 64 || q.size(3) == 128) &&
+                  q.size(2) >= 1,
+              "q must be a device tensor [B,H,N,D] with N >= 1 and head dim D = 64 or 128");
   TORCH_CHECK(k.dim() == 4 && k.size(0) == q.size(0) && k.size(2) == q.size(2) &&
-                  k.size(3) == kAttnD && k.size(1) >= 1 && k.size(1) <= q.size(1) &&
+                  k.size(3) == q.size(3) && k.size(1) >= 1 && k.size(1) <= q.size(1) &&
                   q.size(1) % k.size(1) == 0,
-              "k must be [B,Hkv,N,64] with q's B and N (self-attention geometry) and a head "
-              "count Hkv that divides q's: got ", k.sizes(), " for q ", q.sizes());
+              "k must be [B,Hkv,N,D] with q's B, N and head dim D (64 or 128; self-attention "
+              "geometry) and a head count Hkv that divides q's: got ", k.sizes(), " for q ",
+              q.sizes());
   auto check = [&](const NamedTensor& a, at::ScalarType dtype, bool layout, const char* want) {
     TORCH_CHECK(a.second.scalar_type() == dtype && a.second.device() == q.device() && layout,
                 a.first, " must be ", want, " on q's device");
@@ -573,7 +577,7 @@ static int check_attn_args(const at::Tensor& q, const at::Tensor& k, NamedTensor
   }
   for (const NamedTensor& a : strided_like_k) {
     check(a, at::kBFloat16, a.second.sizes() == k.sizes() && a.second.stride(3) == 1,
-          "bf16, shaped like k ([B,Hkv,N,64]), last dim contiguous,");
+          "bf16, shaped like k ([B,Hkv,N,D]), last dim contiguous,");
   }
   for (const NamedTensor& a : dense_like_q) {
     check(a, at::kBFloat16, a.second.sizes() == q.sizes() && a.second.is_contiguous(),
@@ -581,7 +585,7 @@ static int check_attn_args(const at::Tensor& q, const at::Tensor& k, NamedTensor
   }
   for (const NamedTensor& a : dense_like_k) {
     check(a, at::kBFloat16, a.second.sizes() == k.sizes() && a.second.is_contiguous(),
-          "bf16, shaped like k ([B,Hkv,N,64]), contiguous,");
+          "bf16, shaped like k ([B,Hkv,N,D]), contiguous,");
   }
   for (const NamedTensor& a : row_stats) {
     check(a, at::kFloat, a.second.numel() >= q.size(0) * q.size(1) * q.size(2), "fp32[B*H*N]");
@@ -604,11 +608,23 @@ static const int* checked_doc_start(const c10::optional<at::Tensor>& doc_start,
   return ds.data_ptr<int>();
 }
 
+// Head dim 128: kernels and launchers of their own, attention_d128.h (included
+// at the end of this file, behind the helpers it shares with the decode code).
+constexpr int kAttnD128 = 128;
+static void attn_fwd_d128(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                          at::Tensor& o, at::Tensor& lse, double scale, bool causal,
+                          const int* dsp, int G);
+static void attn_bwd_d128(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                          const at::Tensor& dout, const at::Tensor& o, const at::Tensor& lse,
+                          at::Tensor& dq, at::Tensor& dk, at::Tensor& dv, at::Tensor& delta,
+                          double scale, bool causal, const int* dsp, int G);
+
 void attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
               double scale, bool causal, c10::optional<at::Tensor> doc_start) {
   const int G = check_attn_args(q, k, {{"q", q}}, {{"k", k}, {"v", v}}, {{"o", o}}, {},
                                 {{"lse", lse}});
   const int* dsp = checked_doc_start(doc_start, q, causal);
+  if (q.size(3) == kAttnD128) return attn_fwd_d128(q, k, v, o, lse, scale, causal, dsp, G);
   const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
   auto stream = c10::hip::getCurrentHIPStream();
   static_assert(kKTF % (2 * kQT) == 0); // a wave's 32 q rows also end at N then
@@ -1013,6 +1029,9 @@ void attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout, at::Ten
                                 {{"o", o}, {"dq", dq}}, {{"dk", dk}, {"dv", dv}},
                                 {{"lse", lse}, {"delta", delta}});
   const int* dsp = checked_doc_start(doc_start, q, causal);
+  if (q.size(3) == kAttnD128) {
+    return attn_bwd_d128(q, k, v, dout, o, lse, dq, dk, dv, delta, scale, causal, dsp, G);
+  }
   const int H = q.size(1), N = q.size(2), BH = q.size(0) * H;
   auto stream = c10::hip::getCurrentHIPStream();
 
@@ -1876,5 +1895,7 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
                        (int)chunk, causal);
   }
 }
+
+#include "attention_d128.h"
 
 } // namespace dmlamd

@@ -2,11 +2,14 @@
 
 `sdpa(q, k, v, causal=True)` matches
 F.scaled_dot_product_attention(..., is_causal=causal) for bf16
-[B, H, N, 64] self-attention device tensors of ANY sequence length
-N >= 1: a multiple of 64 runs the aligned kernels, every other length
-their ragged instantiation (clamped loads, masked tail, predicated
-stores — ops/csrc/attention.hip). Anything else (other head dims,
-cross-attention geometry, non-bf16) falls back to torch SDPA
+[B, H, N, D] self-attention device tensors with head dim D = 64 or 128
+and ANY sequence length N >= 1: a multiple of 64 runs the aligned
+kernels, every other length their ragged instantiation (clamped loads,
+masked tail, predicated stores — ops/csrc/attention.hip; the D = 128
+kernels, with every option of the D = 64 ones, are
+ops/csrc/attention_d128.h, verified in tests/test_gpu_attention_d128.py).
+Anything else (other head dims, cross-attention geometry, non-bf16)
+falls back to torch SDPA
 (AOTriton); `fused_attention_usable(q, k, v)` tells which path a call
 takes. The fused path is ON by default whenever usable — set
 DMLCLOUD_DISABLE_FUSED_ATTN=1 to force the AOTriton path (the A/B
@@ -99,7 +102,7 @@ def _usable(q, k, v, doc_start=None, causal=True):
         and is_available()
         and q.dtype == torch.bfloat16
         and q.dim() == 4
-        and q.shape[-1] == 64
+        and q.shape[-1] in (64, 128)
         and q.shape[-2] >= 1
         and k.dim() == 4
         and k.shape[0] == q.shape[0]
@@ -128,8 +131,8 @@ def _usable(q, k, v, doc_start=None, causal=True):
 def fused_attention_usable(q, k, v, doc_start=None, causal=True) -> bool:
     """True when `sdpa(q, k, v, causal, doc_start)` will run the native
     MFMA kernels, False when it will fall back to torch SDPA: exactly the
-    decision `sdpa` makes (bf16 device tensors, q [B, H, N, 64] with any
-    N >= 1, k and v shaped like q or, for grouped-query attention, alike
+    decision `sdpa` makes (bf16 device tensors, q [B, H, N, D] with D = 64
+    or 128 and any N >= 1, k and v shaped like q or, for grouped-query attention, alike
     with a head count that divides H, extension built, no
     DMLCLOUD_DISABLE_FUSED_ATTN; with a `doc_start` also causal=True and
     an integer [B, N] tensor on q's device). `causal` only matters when
@@ -221,7 +224,10 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
     attention to the query's own document. It takes no gradient.
 
     k and v may have fewer heads than q (grouped-query attention, see the
-    module docstring), on the native path and on the fallback alike."""
+    module docstring), on the native path and on the fallback alike.
+
+    The native path serves head dims 64 and 128, each with kernels of its
+    own and the same options (any N, strides, doc_start, GQA)."""
     if _usable(q, k, v, doc_start, causal):
         scale = 1.0 / math.sqrt(q.shape[-1])
         q = q if _lastdim_ok(q) else q.contiguous()
@@ -308,7 +314,8 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     head: R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16 the
     tiled ones (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four per
     block, key tiles past a tile's last causal position skipped). Everything
-    else runs `_attention_ref.kvcache_attention_ref`.
+    else runs `_attention_ref.kvcache_attention_ref`; that includes head dim
+    128, which `sdpa` serves natively but the decode kernels do not yet.
 
     Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
     lse [B, H, Nq] fp32."""

@@ -11,6 +11,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py --gqa      # the GQA section alone
     python tools/bench_attn.py --decode   # KV-cache decode (sdpa_kvcache) alone
     python tools/bench_attn.py --decode-tiled   # sdpa_kvcache, more than 16 columns
+    python tools/bench_attn.py --d128     # head dim 128: native against the torch SDPA fallback
 """
 
 import math
@@ -278,7 +279,65 @@ def main_gqa():
     bench_gqa(16, 16, 2, 2048)  # 1024 dK/dV blocks, each 8 heads long
 
 
+def bench_d128(b, h, hkv, n, docs=False, rounds=3):
+    """Head dim 128, causal, through `sdpa`: forward and forward+backward,
+    the native kernels against the fallback (DMLCLOUD_DISABLE_FUSED_ATTN=1:
+    torch SDPA, with the boolean mask for documents), the two alternating
+    over `rounds` rounds in one process. Prints median and min..max per
+    cell, the achieved TF of the medians and the fallback / native ratio."""
+    from dmlcloud_amd.ops.fused_attn import document_starts, sdpa
+
+    d = 128
+    torch.manual_seed(0)
+    mk = lambda heads: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16).requires_grad_(True)
+    q, k, v = mk(h), mk(hkv), mk(hkv)
+    do = (torch.randn(b, h, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    kw = {}
+    if docs:  # documents of 512 tokens, a ragged one first
+        ids = ((torch.arange(n, device=DEV) + 200) // 512).expand(b, n)
+        kw = {'doc_start': document_starts(ids)}
+
+    def fwd():
+        with torch.no_grad():
+            sdpa(q, k, v, causal=True, **kw)
+
+    def fwd_bwd():
+        q.grad = k.grad = v.grad = None
+        sdpa(q, k, v, causal=True, **kw).backward(do)
+
+    times = {}
+    for _ in range(rounds):
+        for path, off in (('native', '0'), ('torch', '1')):
+            os.environ['DMLCLOUD_DISABLE_FUSED_ATTN'] = off
+            for name, fn in (('fwd', fwd), ('fwd+bwd', fwd_bwd)):
+                times.setdefault((path, name), []).append(time_fn(fn, reps=10, warmup=3))
+    os.environ['DMLCLOUD_DISABLE_FUSED_ATTN'] = '0'
+    flops = 4 * b * h * n * n * d * 0.5  # dense causal count, also for the document row
+    for name, mult in (('fwd', 1.0), ('fwd+bwd', 3.5)):
+        cell = {}
+        for path in ('native', 'torch'):
+            t = sorted(times[(path, name)])
+            cell[path] = t[len(t) // 2]
+            cell[path + '_txt'] = f'{cell[path]:9.1f}us [{t[0]:.1f}..{t[-1]:.1f}] ({flops * mult / cell[path] / 1e6:6.1f} TF)'
+        print(
+            f'D128 {name:7s} B={b} H={h} Hkv={hkv} N={n}{" docs" if docs else ""}: native {cell["native_txt"]} '
+            f'| torch {cell["torch_txt"]} | torch/native {cell["torch"] / cell["native"]:4.2f}x',
+            flush=True,
+        )
+
+
+def main_d128():
+    bench_d128(8, 16, 16, 1024)
+    bench_d128(8, 16, 16, 2048)
+    bench_d128(4, 16, 16, 4096)
+    bench_d128(8, 16, 4, 2048)  # GQA
+    bench_d128(8, 16, 16, 2048, docs=True)  # packed documents
+
+
 if __name__ == '__main__':
+    if '--d128' in sys.argv[1:]:
+        main_d128()
+        sys.exit(0)
     if '--decode' in sys.argv[1:]:
         main_decode()
         sys.exit(0)
