@@ -16,6 +16,10 @@
 //                         more than 16 query columns per K/V head, up to four
 //                         16-column tiles per block (see "KV-cache, more than
 //                         16 columns").
+//   attn_decode_d128_kernel / attn_decode_d128_merge_kernel: the KV-cache
+//                         kernels at head dim 128, one pair for any number
+//                         of columns (attention_decode_d128.h, included at
+//                         the end).
 // Fragment maps of v_mfma_f32_16x16x32_bf16, empirically confirmed
 // (profiles/mfma_16x16x32_bf16_layout.txt):
 //   A (bf16x8): lane l elem j <-> A[l%16][8*(l/16)+j]
@@ -1803,9 +1807,12 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_tiled_merg
 static int64_t tiled_tiles(int64_t R) { return ceil_div(R, kDecCols); }
 static int64_t tiled_groups(int64_t R) { return ceil_div(tiled_tiles(R), kTileGroup); }
 
-int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S) {
+// D = 64 or 128: the head dim, the width of an O partial's 16 rows.
+int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S,
+                                           int64_t D) {
+  TORCH_CHECK(D == kAttnD || D == kAttnD128, "attn_decode_tiled: head dim must be 64 or 128, got ", D);
   // one partial per (b, K/V head, column tile, split); S == 1 stores directly
-  return S > 1 ? B * Hkv * tiled_tiles(R) * S * (kDecPartO + kDecPartML) : 0;
+  return S > 1 ? B * Hkv * tiled_tiles(R) * S * (kDecCols * D + kDecPartML) : 0;
 }
 
 // The split count a call runs with: `num_splits` when positive, else
@@ -1830,21 +1837,28 @@ int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax
                   max_splits);
 }
 
+// Head dim 128: a kernel pair and a launcher of its own,
+// attention_decode_d128.h (included at the end of this file).
+static void attn_decode_tiled_d128(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                   const at::Tensor& kv_len, at::Tensor& o, at::Tensor& lse,
+                                   at::Tensor& ws, double scale, bool causal, int64_t S,
+                                   int64_t chunk);
+
 void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
                        at::Tensor lse, at::Tensor ws, double scale, bool causal,
                        int64_t num_splits) {
-  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.size(3) == kAttnD && q.size(2) >= 1 &&
-                  q.size(0) >= 1 && q.scalar_type() == at::kBFloat16,
-              "q must be a bf16 device tensor [B,H,Nq,64] with B, Nq >= 1 (head dim 64 only)");
-  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2);
-  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == kAttnD && k.size(1) >= 1 &&
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4 && (q.size(3) == kAttnD || q.size(3) == kAttnD128) &&
+                  q.size(2) >= 1 && q.size(0) >= 1 && q.scalar_type() == at::kBFloat16,
+              "q must be a bf16 device tensor [B,H,Nq,D] with B, Nq >= 1 and head dim D = 64 or 128");
+  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
+  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == D && k.size(1) >= 1 &&
                   H % k.size(1) == 0 && H >= 1,
-              "k_cache must be [B,Hkv,Nmax,64] with q's B and a head count Hkv that divides q's: "
-              "got ", k.sizes(), " for q ", q.sizes());
+              "k_cache must be [B,Hkv,Nmax,D] with q's B and head dim D and a head count Hkv that "
+              "divides q's: got ", k.sizes(), " for q ", q.sizes());
   const int64_t Hkv = k.size(1), Nmax = k.size(2), G = H / Hkv;
   TORCH_CHECK(v.sizes() == k.sizes(), "v_cache must be shaped like k_cache");
   TORCH_CHECK(Nmax >= Nq, "the cache must hold the Nq new rows: Nmax ", Nmax, " < Nq ", Nq);
-  TORCH_CHECK(Nmax <= INT32_MAX - 2 * kDecChunkAlign && B * H * Nq <= INT32_MAX / kAttnD,
+  TORCH_CHECK(Nmax <= INT32_MAX - 2 * kDecChunkAlign && B * H * Nq <= INT32_MAX / D,
               "attn_decode_tiled: Nmax or B*H*Nq too large");
   const int64_t R = G * Nq;
   for (const NamedTensor& a : {NamedTensor{"q", q}, {"k_cache", k}, {"v_cache", v}}) {
@@ -1867,7 +1881,7 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
                   lse.numel() == B * H * Nq && lse.is_contiguous(),
               "lse must be fp32 [B,H,Nq], contiguous, on q's device");
   const int64_t S = attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device());
-  const int64_t ws_floats = attn_decode_tiled_workspace_floats(B, Hkv, R, S);
+  const int64_t ws_floats = attn_decode_tiled_workspace_floats(B, Hkv, R, S, D);
   TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.device() == q.device() && ws.is_contiguous() &&
                   ws.numel() >= ws_floats && (ws.numel() == 0 || (uintptr_t)ws.data_ptr() % 16 == 0),
               "the workspace must be fp32, contiguous, 16-byte aligned, on q's device, with >= ",
@@ -1877,6 +1891,7 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
   const int64_t chunk = ceil_div(ceil_div(Nmax, S), kDecChunkAlign) * kDecChunkAlign;
   TORCH_CHECK(B * Hkv * groups * S <= INT32_MAX && S * chunk <= INT32_MAX,
               "attn_decode_tiled: too many blocks or keys");
+  if (D == kAttnD128) return attn_decode_tiled_d128(q, k, v, kv_len, o, lse, ws, scale, causal, S, chunk);
 
   auto stream = c10::hip::getCurrentHIPStream();
   float* ws_o = S > 1 ? ws.data_ptr<float>() : nullptr;
@@ -1897,5 +1912,6 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
 }
 
 #include "attention_d128.h"
+#include "attention_decode_d128.h"
 
 } // namespace dmlamd

@@ -78,7 +78,8 @@ int64_t attn_decode_splits(int64_t B, int64_t Hkv, int64_t Nmax, int64_t num_spl
 void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
                        at::Tensor lse, at::Tensor ws, double scale, bool causal,
                        int64_t num_splits);
-int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S);
+int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S,
+                                           int64_t D);
 int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax,
                                  int64_t num_splits, int64_t device);
 
@@ -144,12 +145,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("B"), py::arg("Hkv"), py::arg("Nmax"), py::arg("num_splits"), py::arg("device"));
   m.def("attn_decode_tiled", &dmlamd::attn_decode_tiled,
         "Tiled split-KV attention over a K/V cache for any R = (H/Hkv)*Nq >= 1 columns per K/V "
-        "head: 16-column MFMA tiles, up to four per block (MFMA bf16, D=64; num_splits 0 = auto)",
+        "head: 16-column MFMA tiles, up to four per block (MFMA bf16, D=64 or 128 by q's last "
+        "dim; num_splits 0 = auto)",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"), py::arg("o"),
         py::arg("lse"), py::arg("ws"), py::arg("scale"), py::arg("causal"), py::arg("num_splits"));
   m.def("attn_decode_tiled_workspace_floats", &dmlamd::attn_decode_tiled_workspace_floats,
-        "fp32 elements attn_decode_tiled's workspace needs for R columns and S splits",
-        py::arg("B"), py::arg("Hkv"), py::arg("R"), py::arg("S"));
+        "fp32 elements attn_decode_tiled's workspace needs for R columns, S splits and head dim D",
+        py::arg("B"), py::arg("Hkv"), py::arg("R"), py::arg("S"), py::arg("D") = 64);
   m.def("attn_decode_tiled_splits", &dmlamd::attn_decode_tiled_splits,
         "The split count attn_decode_tiled runs with (num_splits, or the automatic choice for 0)",
         py::arg("B"), py::arg("Hkv"), py::arg("R"), py::arg("Nmax"), py::arg("num_splits"),

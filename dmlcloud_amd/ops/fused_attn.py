@@ -42,13 +42,15 @@ tests/test_gpu_attention_docmask.py.
 
 Decoding: `sdpa_kvcache(q, k_cache, v_cache, kv_len)` attends new query
 rows (one token, a few draft tokens, a chunk of a prompt) to a partly
-filled [B, Hkv, Nmax, 64] K/V cache whose per-row lengths live on the
-device. It has kernels of its own (split-KV decode plus a merge pass, and
-their tiled form for more than 16 query columns per K/V head,
-ops/csrc/attention.hip) and never goes through `sdpa`,
+filled [B, Hkv, Nmax, D] K/V cache (D = 64 or 128) whose per-row lengths
+live on the device. It has kernels of its own (D = 64: split-KV decode plus
+a merge pass, and their tiled form for more than 16 query columns per K/V
+head, ops/csrc/attention.hip; D = 128: one tiled pair for any number of
+columns, ops/csrc/attention_decode_d128.h) and never goes through `sdpa`,
 whose behaviour for kv length != q length (torch SDPA, top-left causal)
-is unchanged. Verified in tests/test_gpu_attention_kvcache.py and
-tests/test_gpu_attention_kvcache_tiled.py.
+is unchanged. Verified in tests/test_gpu_attention_kvcache.py,
+tests/test_gpu_attention_kvcache_tiled.py and
+tests/test_gpu_attention_kvcache_d128.py.
 """
 
 import math
@@ -254,10 +256,10 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len):
         and is_available()
         and q.dtype == torch.bfloat16
         and q.dim() == 4
-        and q.shape[-1] == 64
+        and q.shape[-1] in (64, 128)
         and k_cache.dim() == 4
         and k_cache.shape[0] == q.shape[0]
-        and k_cache.shape[3] == 64
+        and k_cache.shape[3] == q.shape[-1]
         and k_cache.shape[1] >= 1
         and q.shape[1] % k_cache.shape[1] == 0
         and (q.shape[1] // k_cache.shape[1]) * q.shape[2] >= 1
@@ -277,8 +279,8 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len):
 def fused_kvcache_usable(q, k_cache, v_cache, kv_len) -> bool:
     """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len)` will run the
     native split-KV kernels, False when it will run the pure-torch
-    reference: bf16 device tensors, q [B, H, Nq, 64] with any Nq >= 1,
-    caches [B, Hkv, Nmax, 64] with Hkv dividing H, Nmax >= Nq, last dims
+    reference: bf16 device tensors, q [B, H, Nq, D] with D = 64 or 128 and
+    any Nq >= 1, caches [B, Hkv, Nmax, D] with Hkv dividing H, Nmax >= Nq, last dims
     contiguous, an integer [B] kv_len on q's device,
     extension built, no DMLCLOUD_DISABLE_FUSED_ATTN."""
     return bool(_kvcache_usable(q, k_cache, v_cache, kv_len))
@@ -309,13 +311,15 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     contents may change between replays. The keys are split over
     `num_splits` blocks per (b, K/V head), 0 = chosen from the shapes and
     the device's CU count, and merged by a second kernel; any batch / head /
-    row strides pass without a copy ([B, Nmax, Hkv, 64] memory viewed
+    row strides pass without a copy ([B, Nmax, Hkv, D] memory viewed
     transposed included). R = (H / Hkv) * Nq query columns share a K/V
-    head: R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16 the
-    tiled ones (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four per
-    block, key tiles past a tile's last causal position skipped). Everything
-    else runs `_attention_ref.kvcache_attention_ref`; that includes head dim
-    128, which `sdpa` serves natively but the decode kernels do not yet.
+    head. D = 64: R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16
+    the tiled ones (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four
+    per block, key tiles past a tile's last causal position skipped). D = 128
+    has one kernel pair of the tiled form for every R
+    (ops/csrc/attention_decode_d128.h), reached through
+    `_C.attn_decode_tiled` as well. Everything else (other head dims, other
+    dtypes) runs `_attention_ref.kvcache_attention_ref`.
 
     Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
     lse [B, H, Nq] fp32."""
@@ -330,12 +334,12 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     q, k_cache, v_cache = (t if _vector_loadable(t) else t.contiguous() for t in (q, k_cache, v_cache))
     kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
     R = (H // Hkv) * Nq
-    if R > 16:
+    if R > 16 or D == 128:
         splits = _C.attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device())
         o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
         lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
         # one partial per (column tile, split); every element the merge reads is written
-        ws = torch.empty(_C.attn_decode_tiled_workspace_floats(B, Hkv, R, splits), dtype=torch.float32, device=q.device)
+        ws = torch.empty(_C.attn_decode_tiled_workspace_floats(B, Hkv, R, splits, D), dtype=torch.float32, device=q.device)
         _C.attn_decode_tiled(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits)
         return (o, lse) if return_lse else o
     splits = _C.attn_decode_splits(B, Hkv, Nmax, num_splits, q.get_device())

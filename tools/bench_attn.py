@@ -11,6 +11,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py --gqa      # the GQA section alone
     python tools/bench_attn.py --decode   # KV-cache decode (sdpa_kvcache) alone
     python tools/bench_attn.py --decode-tiled   # sdpa_kvcache, more than 16 columns
+    python tools/bench_attn.py --decode-d128    # sdpa_kvcache at head dim 128
     python tools/bench_attn.py --d128     # head dim 128: native against the torch SDPA fallback
 """
 
@@ -273,6 +274,48 @@ def main_decode_tiled():
         bench_decode_tiled(1, 12, 12, 512, 4096)
 
 
+def bench_decode_d128(b, h, hkv, nq, nmax):
+    """Head dim 128, Nq new causal rows over a FULL cache, kv_len = Nmax:
+    native (attn_decode_d128_kernel) with the automatic split count | native
+    num_splits=1 | kvcache_attention_ref on the device (what sdpa_kvcache ran
+    at D = 128 before these kernels) | for Nq = 1, the D = 64 native kernels
+    at twice the head count: the same K + V bytes."""
+    from dmlcloud_amd.ops._attention_ref import kvcache_attention_ref
+    from dmlcloud_amd.ops.fused_attn import fused_kvcache_usable, sdpa_kvcache
+
+    torch.manual_seed(0)
+    mk = lambda heads, n, d: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    q, k, v = mk(h, nq, 128), mk(hkv, nmax, 128), mk(hkv, nmax, 128)
+    kv_len = torch.full((b,), nmax, dtype=torch.int32, device=DEV)
+    assert fused_kvcache_usable(q, k, v, kv_len)
+    with torch.no_grad():
+        t_auto = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len), reps=200, warmup=20)
+        t_one = time_fn(lambda: sdpa_kvcache(q, k, v, kv_len, num_splits=1), reps=200, warmup=20)
+        t_ref = time_fn(lambda: kvcache_attention_ref(q, k, v, kv_len, True, False), reps=200, warmup=20)
+        line = ''
+        if nq == 1:
+            q6, k6, v6 = mk(2 * h, 1, 64), mk(2 * hkv, nmax, 64), mk(2 * hkv, nmax, 64)
+            t_d64 = time_fn(lambda: sdpa_kvcache(q6, k6, v6, kv_len), reps=200, warmup=20)
+            line = f' | D=64 native H={2 * h} Hkv={2 * hkv} (same bytes) {t_d64:8.1f}us ({t_auto / t_d64:4.2f}x of it)'
+    splits = _C.attn_decode_tiled_splits(b, hkv, h // hkv * nq, nmax, 0, 0)
+    best = min(t_auto, t_one)
+    print(
+        f'DECODE-D128 B={b} H={h} Hkv={hkv} Nq={nq} Nmax={nmax}: native S={splits} {t_auto:8.1f}us '
+        f'| native S=1 {t_one:8.1f}us | torch reference {t_ref:8.1f}us ({t_ref / best:5.2f}x the better native)' + line,
+        flush=True,
+    )
+
+
+def main_decode_d128():
+    for rnd in range(3):  # three rounds in one session: the spread
+        print(f'-- round {rnd + 1}')
+        bench_decode_d128(8, 6, 6, 1, 1024)
+        bench_decode_d128(8, 6, 6, 1, 4096)
+        bench_decode_d128(8, 32, 8, 1, 4096)
+        bench_decode_d128(8, 6, 6, 32, 1024)
+        bench_decode_d128(1, 8, 8, 512, 4096)
+
+
 def main_gqa():
     bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
     bench_gqa(64, 12, 1, 1024)  # ... and as MQA
@@ -337,6 +380,9 @@ def main_d128():
 if __name__ == '__main__':
     if '--d128' in sys.argv[1:]:
         main_d128()
+        sys.exit(0)
+    if '--decode-d128' in sys.argv[1:]:
+        main_decode_d128()
         sys.exit(0)
     if '--decode' in sys.argv[1:]:
         main_decode()
