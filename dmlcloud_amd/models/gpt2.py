@@ -25,6 +25,14 @@ lengths live on the device and are advanced there, so a step has no host
 sync. `GPT2.extend(idx, cache)` appends a whole chunk of tokens to a cache
 that may already hold some (chunked prefill, `generate(prefill_chunk=c)`,
 the next turn of a conversation) through the same op with Nq = T.
+
+Paged cache: `init_paged_cache` (or `generate(page_size=p)`) keeps K and V
+in pools of fixed-size pages named by a per-row block table
+(`PagedKVCache`) in place of one dense tensor per layer. `prefill`,
+`decode_step` and `extend` take either cache type; on the paged one the new
+rows are written by `ops.fused_attn.kvcache_append` (one launch per layer)
+and read by `sdpa_kvcache(block_table=...)`. The table is fixed when the
+cache is made; a free list or growth is the caller's.
 """
 
 import math
@@ -35,7 +43,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..ops.fused_attn import document_starts, sdpa, sdpa_kvcache
+from ..ops.fused_attn import document_starts, kvcache_append, sdpa, sdpa_kvcache
 from ..ops.fused_ln import LayerNorm
 from ..ops.fused_loss import cross_entropy
 
@@ -117,6 +125,24 @@ class CausalSelfAttention(nn.Module):
         y = sdpa_kvcache(q, k_cache, v_cache, kv_len, causal=True)
         return self.c_proj(y.transpose(1, 2).reshape(B, T, C))
 
+    def prefill_paged(self, x, k_pool, v_pool, kv_len, block_table):
+        """forward(x) that also writes the prompt's K/V through the block
+        table (kv_len already holds T for every row)."""
+        B, T, C = x.shape
+        q, k, v = self._heads(x)
+        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table)
+        return self.c_proj(sdpa(q, k, v, causal=True).transpose(1, 2).reshape(B, T, C))
+
+    def extend_paged(self, x, k_pool, v_pool, kv_len, block_table):
+        """T >= 1 new tokens per row, x [B, T, C], on a paged cache: their K/V
+        go to logical rows kv_len[b] - T + t of the row's pages (one launch),
+        then token t attends logical rows 0..kv_len[b] - T + t."""
+        B, T, C = x.shape
+        q, k, v = self._heads(x)
+        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table)
+        y = sdpa_kvcache(q, k_pool, v_pool, kv_len, causal=True, block_table=block_table)
+        return self.c_proj(y.transpose(1, 2).reshape(B, T, C))
+
 
 class Block(nn.Module):
     def __init__(self, cfg: GPT2Config):
@@ -147,6 +173,14 @@ class Block(nn.Module):
         x = x + self.attn.extend(self.ln_1(x), *cache_args)
         return x + self.mlp(self.ln_2(x))
 
+    def prefill_paged(self, x, *cache_args):
+        x = x + self.attn.prefill_paged(self.ln_1(x), *cache_args)
+        return x + self.mlp(self.ln_2(x))
+
+    def extend_paged(self, x, *cache_args):
+        x = x + self.attn.extend_paged(self.ln_1(x), *cache_args)
+        return x + self.mlp(self.ln_2(x))
+
 
 @dataclass
 class KVCache:
@@ -156,6 +190,21 @@ class KVCache:
     k: List[torch.Tensor]
     v: List[torch.Tensor]
     kv_len: torch.Tensor
+
+
+@dataclass
+class PagedKVCache:
+    """Per-layer K and V page pools, [num_pages, n_kv_head, page_size,
+    head_dim] each; the number of valid rows of every batch row, int32 [B];
+    and the block table, int32 [B, max_pages]: logical row j of batch row b
+    is row j % page_size of page block_table[b, j // page_size]. All on the
+    device."""
+
+    k: List[torch.Tensor]
+    v: List[torch.Tensor]
+    kv_len: torch.Tensor
+    block_table: torch.Tensor
+    page_size: int
 
 
 class GPT2(nn.Module):
@@ -219,24 +268,69 @@ class GPT2(nn.Module):
             kv_len=torch.zeros(batch, dtype=torch.int32, device=device),
         )
 
+    def init_paged_cache(
+        self, batch, max_len, page_size=64, num_pages=None, block_table=None, device=None, dtype=None
+    ) -> PagedKVCache:
+        """An empty paged cache for `batch` rows of up to `max_len` tokens:
+        ceil(max_len / page_size) table entries per row over pools of
+        `num_pages` pages (default: one page per entry). The default table
+        hands the pages out in order; any integer [batch, max_pages] table
+        whose live entries name distinct pages may be passed instead."""
+        cfg = self.cfg
+        device = self.wte.weight.device if device is None else device
+        dtype = self.wte.weight.dtype if dtype is None else dtype
+        n_kv_head = cfg.n_head if cfg.n_kv_head is None else cfg.n_kv_head
+        max_pages = -(-max_len // page_size)
+        if block_table is None:
+            block_table = torch.arange(batch * max_pages, dtype=torch.int32, device=device).view(batch, max_pages)
+        else:
+            assert block_table.shape == (batch, max_pages), 'block_table must be [batch, ceil(max_len / page_size)]'
+            block_table = block_table.to(device=device, dtype=torch.int32).contiguous()
+        num_pages = batch * max_pages if num_pages is None else num_pages
+        shape = (num_pages, n_kv_head, page_size, cfg.n_embd // cfg.n_head)
+        return PagedKVCache(
+            k=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
+            v=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
+            kv_len=torch.zeros(batch, dtype=torch.int32, device=device),
+            block_table=block_table,
+            page_size=page_size,
+        )
+
     @torch.no_grad()
-    def prefill(self, idx, cache: KVCache):
+    def prefill(self, idx, cache):
         """Run the prompt idx [B, T] through the training attention path,
-        fill the cache with its K/V and return the last position's logits
-        [B, vocab]."""
+        fill the cache (either type) with its K/V and return the last
+        position's logits [B, vocab]."""
         B, T = idx.shape
         x = self.wte(idx) + self.wpe(torch.arange(T, device=idx.device))
+        if isinstance(cache, PagedKVCache):
+            cache.kv_len.fill_(T)
+            for block, k_pool, v_pool in zip(self.blocks, cache.k, cache.v):
+                x = block.prefill_paged(x, k_pool, v_pool, cache.kv_len, cache.block_table)
+            return self.lm_head(self.ln_f(x[:, -1]))
         for block, k_cache, v_cache in zip(self.blocks, cache.k, cache.v):
             x = block.prefill(x, k_cache, v_cache)
         cache.kv_len.fill_(T)
         return self.lm_head(self.ln_f(x[:, -1]))
 
+    def _extend_paged(self, idx, cache: PagedKVCache):
+        B, T = idx.shape
+        rows = cache.kv_len.long().unsqueeze(1) + torch.arange(T, device=idx.device)  # before the increment
+        cache.kv_len += T
+        x = self.wte(idx) + self.wpe(rows.clamp(max=self.cfg.n_positions - 1))
+        for block, k_pool, v_pool in zip(self.blocks, cache.k, cache.v):
+            # (a full cache overwrites its last rows instead of writing past them)
+            x = block.extend_paged(x, k_pool, v_pool, cache.kv_len, cache.block_table)
+        return self.lm_head(self.ln_f(x[:, -1]))
+
     @torch.no_grad()
-    def decode_step(self, tokens, cache: KVCache):
-        """Append one token per row (tokens [B]) to the cache and return
-        the logits [B, vocab] for the token after it. Positions come from
-        cache.kv_len on the device; nothing is read back."""
+    def decode_step(self, tokens, cache):
+        """Append one token per row (tokens [B]) to the cache (either type)
+        and return the logits [B, vocab] for the token after it. Positions
+        come from cache.kv_len on the device; nothing is read back."""
         B = tokens.shape[0]
+        if isinstance(cache, PagedKVCache):
+            return self._extend_paged(tokens.view(B, 1), cache)
         pos = cache.kv_len.long()  # the new token's row, before the increment
         cache.kv_len += 1
         batch = torch.arange(B, device=tokens.device)
@@ -247,14 +341,16 @@ class GPT2(nn.Module):
         return self.lm_head(self.ln_f(x[:, 0]))
 
     @torch.no_grad()
-    def extend(self, idx, cache: KVCache):
-        """Append idx [B, T] to a cache that may already hold tokens (each
-        row its own count) and return the last position's logits
+    def extend(self, idx, cache):
+        """Append idx [B, T] to a cache (either type) that may already hold
+        tokens (each row its own count) and return the last position's logits
         [B, vocab]: chunked prefill, or the next turn of a conversation.
         Positions and cache rows come from cache.kv_len on the device;
         nothing is read back. Attention runs through sdpa_kvcache with
         Nq = T."""
         B, T = idx.shape
+        if isinstance(cache, PagedKVCache):
+            return self._extend_paged(idx, cache)
         rows = cache.kv_len.long().unsqueeze(1) + torch.arange(T, device=idx.device)  # [B, T], before the increment
         cache.kv_len += T
         batch = torch.arange(B, device=idx.device).unsqueeze(1)
@@ -265,15 +361,19 @@ class GPT2(nn.Module):
         return self.lm_head(self.ln_f(x[:, -1]))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None, prefill_chunk=None):
+    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None, prefill_chunk=None, page_size=None):
         """idx [B, T] followed by max_new_tokens sampled tokens,
         [B, T + max_new_tokens]. temperature = 0 is greedy; otherwise the
         next token is drawn from softmax(logits / temperature). The prompt
         runs through `prefill` in one piece, or with prefill_chunk = c >= 1
-        through `extend` in pieces of at most c tokens."""
+        through `extend` in pieces of at most c tokens. page_size = p keeps
+        the K/V cache in pages of p rows (`init_paged_cache`)."""
         B, T = idx.shape
         assert T >= 1 and T + max_new_tokens <= self.cfg.n_positions, 'sequence exceeds n_positions'
-        cache = self.init_cache(B, T + max_new_tokens)
+        if page_size is None:
+            cache = self.init_cache(B, T + max_new_tokens)
+        else:
+            cache = self.init_paged_cache(B, T + max_new_tokens, page_size)
         out = [idx]
         if prefill_chunk is None:
             logits = self.prefill(idx, cache)

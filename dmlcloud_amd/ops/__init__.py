@@ -262,6 +262,7 @@ from .fused_attn import (  # noqa: E402,F401
     fused_attention_enabled,
     fused_attention_usable,
     fused_kvcache_usable,
+    kvcache_append,
     sdpa,
     sdpa_kvcache,
 )

@@ -439,7 +439,39 @@ def gqa_bwd_padded(do, q, k, v, o, lse, causal=True, scale=None, doc_start=None)
 # ---------------------------------------------------------------------------
 
 
-def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=False):
+def gather_pages(pool, block_table):
+    """The dense [B, Hkv, max_pages * page_size, D] cache that a block table
+    describes: logical key j of batch row b is row j % page_size of page
+    block_table[b, j // page_size] of pool [num_pages, Hkv, page_size, D].
+    Entries are clamped to [0, num_pages - 1], as the kernels clamp them."""
+    num_pages, Hkv, page_size, D = pool.shape
+    B, max_pages = block_table.shape
+    pages = pool[block_table.long().clamp(0, num_pages - 1)]  # [B, max_pages, Hkv, page_size, D]
+    return pages.transpose(1, 2).reshape(B, Hkv, max_pages * page_size, D)
+
+
+def kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
+    """Index writes of `ops.fused_attn.kvcache_append`: row i of batch row b
+    goes to logical position clamp(kv_len[b], Nq, capacity) - Nq + i, which is
+    cache row (b, :, pos) without a table and row pos % page_size of page
+    block_table[b, pos // page_size] (clamped to the pool) with one."""
+    B, Hkv, Nq, D = k_new.shape
+    page_size = k_cache.shape[2]
+    capacity = page_size * (1 if block_table is None else block_table.shape[1])
+    assert capacity >= Nq and v_cache.shape == k_cache.shape and v_new.shape == k_new.shape
+    ln = kv_len.long().clamp(Nq, capacity)
+    pos = ln[:, None] - Nq + torch.arange(Nq, device=k_new.device)[None, :]  # [B, Nq]
+    if block_table is None:
+        page, row = torch.arange(B, device=k_new.device)[:, None].expand(B, Nq), pos
+    else:
+        page = block_table.long().gather(1, pos // page_size).clamp(0, k_cache.shape[0] - 1)
+        row = pos % page_size
+    # index result [B, Nq, Hkv, D]
+    k_cache[page, :, row] = k_new.transpose(1, 2).to(k_cache.dtype)
+    v_cache[page, :, row] = v_new.transpose(1, 2).to(v_cache.dtype)
+
+
+def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=False, block_table=None):
     """fp32 masked softmax of a few new query rows over the valid part of a
     K/V cache: the CPU path and the test oracle of `sdpa_kvcache`.
 
@@ -449,7 +481,14 @@ def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=F
     sits at p = kv_len[b] - Nq + i and attends keys 0..p (causal) or
     0..kv_len[b] - 1. Cache rows at or past kv_len[b] may hold anything,
     NaN included: their scores are replaced and their V rows zeroed before
-    any product. Returns o in q's dtype (and lse [B, H, Nq] fp32)."""
+    any product. With an integer block_table [B, max_pages] the caches are
+    page pools [num_pages, Hkv, page_size, D] (any page_size >= 1): the pages
+    are gathered into a dense cache of max_pages * page_size rows first
+    (`gather_pages`; dead entries may name any page, their rows are masked).
+    Returns o in q's dtype (and lse [B, H, Nq] fp32)."""
+    if block_table is not None:
+        assert v_cache.shape == k_cache.shape and block_table.shape[0] == q.shape[0]
+        k_cache, v_cache = gather_pages(k_cache, block_table), gather_pages(v_cache, block_table)
     B, H, Nq, D = q.shape
     Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
     assert v_cache.shape == k_cache.shape and H % Hkv == 0 and Nmax >= Nq

@@ -20,6 +20,11 @@
 //                         kernels at head dim 128, one pair for any number
 //                         of columns (attention_decode_d128.h, included at
 //                         the end).
+//   attn_decode_tiled_kernel<true> / attn_decode_d128_kernel<true>: the same
+//                         two over a PAGED cache, page pools read through a
+//                         block table (see StridesPaged).
+//   kvcache_append_kernel writes new K/V rows into a dense or paged cache
+//                         (attention_kvcache_append.h, included at the end).
 // Fragment maps of v_mfma_f32_16x16x32_bf16, empirically confirmed
 // (profiles/mfma_16x16x32_bf16_layout.txt):
 //   A (bf16x8): lane l elem j <-> A[l%16][8*(l/16)+j]
@@ -1539,16 +1544,83 @@ void attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at
 //     order.
 constexpr int kTileGroup = kWavesPerBlock; // column tiles of one block, at most
 
+// Paged KV cache: attn_decode_tiled_kernel and attn_decode_d128_kernel take a
+// `kPaged` template flag. <false> is the dense-cache code, unchanged. <true>:
+// k and v are page POOLS [num_pages, Hkv, page_size, D] (Strides::b is the page
+// stride) and block_table int32 [B, max_pages] names the pages of every batch
+// row: logical key j of row b is row j % page_size of page
+// block_table[b][j / page_size]. The capacity max_pages * page_size takes the
+// place of Nmax (the kernels' `Nmax` argument IS the capacity), so decode_len,
+// the split chunking, positions, lim, lim_max, the wipe and the "exactly
+// once" argument read as before. page_size % 32 == 0 (launcher) and every
+// walked tile starts at a multiple of 32 (k_begin is a multiple of 128), so
+// a 32-key tile lies in ONE page and its page id is one wave-uniform integer:
+//   * the id is read by a uniform (scalar) load, clamped to
+//     [0, num_pages - 1] (the dstart() rule: a malformed table gives wrong
+//     numbers, never an address outside the pools), and becomes two scalar
+//     base pointers (K, V) to which the lanes add their clamped LOGICAL row;
+//   * the chain entry -> base -> K/V loads is kept off the loads' path: the
+//     entry of the tile after next is fetched right after the next tile's
+//     K/V loads are issued and rests in a scalar register through a whole
+//     tile of math before it is turned into bases;
+//   * a wave re-reads the entry for every tile, also when consecutive tiles
+//     share a page (a scalar-cache hit; see docs/KERNELS.md "Paged KV cache").
+// The table, its row length and the page geometry ride in the K stride
+// argument, a StridesPaged<kPaged>, for the reason doc_start rides in a
+// StridesDoc: the <false> argument layout and instruction stream stay.
+template <bool kPaged>
+struct StridesPaged : Strides {
+  const int* table; // block_table, [B, max_pages] contiguous
+  int max_pages, page_size, num_pages;
+};
+template <>
+struct StridesPaged<false> : Strides {};
+
+// A batch row's slice of the block table as the kernels read it: through the
+// constant address space. Nothing writes the table while a kernel runs, and a
+// load from a wave-uniform constant address is a scalar load whatever else
+// the loop holds (a plain global load loses that to the loop's scheduling
+// barrier, which counts as a possible write).
+typedef const int __attribute__((address_space(4))) * PageTable;
+
+// A wave's place in its batch row's block table: the table index of a page
+// and the logical key of that page's row 0.
+struct PageWalk {
+  int pg, key_lo;
+};
+
+// Advance to the page that holds logical key `key` >= w.key_lo: at most
+// key_step / page_size <= 4 scalar rounds.
+kDecodeFn __device__ __forceinline__ void page_seek(PageWalk& w, int key, int page_size) {
+  while (key >= w.key_lo + page_size) {
+    w.key_lo += page_size;
+    ++w.pg;
+  }
+}
+
+// The K and V pointers to which a lane adds (logical key) * row stride, for
+// K/V head kvh of the page named by table value `entry`, whose row 0 is
+// logical key `key_lo`.
+kDecodeFn __device__ __forceinline__ void page_bases(
+    int entry, int key_lo, int kvh, const __hip_bfloat16* k, const __hip_bfloat16* v,
+    const StridesPaged<true>& sk, const Strides& sv, const __hip_bfloat16*& kt,
+    const __hip_bfloat16*& vt) {
+  const int64_t page = min(max(entry, 0), sk.num_pages - 1);
+  kt = k + page * sk.b + (int64_t)kvh * sk.h - (int64_t)key_lo * sk.r;
+  vt = v + page * sv.b + (int64_t)kvh * sv.h - (int64_t)key_lo * sv.r;
+}
+
 // amdgpu_waves_per_eu(4): the block's LDS admits four blocks per CU, the
 // decode kernel's occupancy; left alone the allocator takes 130 registers,
 // two more than four waves per SIMD allow.
+template <bool kPaged>
 kDecodeFn __global__ void __launch_bounds__(kAttnThreads) __attribute__((amdgpu_waves_per_eu(4)))
 attn_decode_tiled_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const int* __restrict__ kv_len,
     __hip_bfloat16* __restrict__ o, float* __restrict__ lse, float* __restrict__ ws_o,
     float* __restrict__ ws_ml, int H, int G, int Nq, int Nmax, int S, int chunk, float scale,
-    bool causal, Strides sq, Strides sk, Strides sv) {
+    bool causal, Strides sq, StridesPaged<kPaged> sk, Strides sv) {
   __shared__ DecodeWaveLds wave_lds[kWavesPerBlock];
   __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStride];
 
@@ -1624,19 +1696,22 @@ attn_decode_tiled_kernel(
   const __hip_bfloat16* kp = k + (int64_t)b * sk.b + (int64_t)kvh * sk.h;
   const __hip_bfloat16* vp = v + (int64_t)b * sv.b + (int64_t)kvh * sv.h;
   // K fragments [16-key half h][k-chunk c] and V pieces of the tile at key0,
-  // every row clamped to len - 1; K before V, pinned (see the decode kernel)
-  auto load_tile = [&](int key0, bf16x8(&kf)[2][2], bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
+  // every row clamped to len - 1; K before V, pinned (see the decode kernel).
+  // kt / vt: the tile's page_bases() (paged); the dense code keeps reading
+  // its (b, K/V head) slices kp / vp.
+  auto load_tile = [&](int key0, const __hip_bfloat16* kt, const __hip_bfloat16* vt,
+                       bf16x8(&kf)[2][2], bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int64_t kr = min(key0 + 16 * h + row16, len - 1);
 #pragma unroll
-      for (int c = 0; c < 2; ++c) kf[h][c] = *(const bf16x8*)(kp + kr * sk.r + 32 * c + 8 * grp);
+      for (int c = 0; c < 2; ++c) kf[h][c] = *(const bf16x8*)((kPaged ? kt : kp) + kr * sk.r + 32 * c + 8 * grp);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
       const int64_t vr = min(key0 + st_row + 8 * x, len - 1);
-      vpc[x] = *(const bf16x8*)(vp + vr * sv.r + st_col);
+      vpc[x] = *(const bf16x8*)((kPaged ? vt : vp) + vr * sv.r + st_col);
     }
   };
   auto stage_v = [&](int buf, const bf16x8(&vpc)[4]) kDecodeFn __attribute__((always_inline)) {
@@ -1656,8 +1731,30 @@ attn_decode_tiled_kernel(
   int key0 = k_begin + phase * kKT;
   bool have = key0 < k_stop;
   bf16x8 kf[2][2], vpc[4];
+  // Paged: a walked tile key0 < k_stop <= len lies in an allocated page, index
+  // key0 / page_size <= (len - 1) / page_size < max_pages (len <= capacity),
+  // so only table entries < ceil(len / page_size) are read. Its clamped rows
+  // min(key0 + x, len - 1), x < 32, stay in [key0, key0 + 31]: the same
+  // 32-aligned tile, hence the same page (page_size % 32 == 0), rows
+  // 0..page_size-1 of a page id clamped into the pool. `walk` only ever
+  // seeks to a tile that exists, so the entry it names is one of those.
+  const __hip_bfloat16 *kt = kp, *vt = vp; // paged: the current tile's bases
+  [[maybe_unused]] PageWalk walk = {0, 0};
+  [[maybe_unused]] int ent_next = 0, lo_next = 0; // the NEXT tile's entry and page start
+  [[maybe_unused]] PageTable tbl = nullptr; // block_table[b]
+  if constexpr (kPaged) {
+    if (have) {
+      tbl = (PageTable)(sk.table + (int64_t)b * sk.max_pages);
+      walk.pg = key0 / sk.page_size;
+      walk.key_lo = walk.pg * sk.page_size;
+      page_bases(tbl[walk.pg], walk.key_lo, kvh, k, v, sk, sv, kt, vt);
+      if (key0 + key_step < k_stop) page_seek(walk, key0 + key_step, sk.page_size);
+      ent_next = tbl[walk.pg];
+      lo_next = walk.key_lo;
+    }
+  }
   if (have) {
-    load_tile(key0, kf, vpc);
+    load_tile(key0, kt, vt, kf, vpc);
     stage_v(0, vpc);
   }
   int buf = 0;
@@ -1666,7 +1763,17 @@ attn_decode_tiled_kernel(
     const int key_next = key0 + key_step;
     const bool has_next = key_next < k_stop;
     bf16x8 kf_next[2][2];
-    if (has_next) load_tile(key_next, kf_next, vpc);
+    if constexpr (kPaged) page_bases(ent_next, lo_next, kvh, k, v, sk, sv, kt, vt);
+    if (has_next) load_tile(key_next, kt, vt, kf_next, vpc);
+    if constexpr (kPaged) {
+      // the entry of the tile after next, behind the loads just issued; it
+      // is first used at the top of the next round (the compiler sinks this
+      // scalar load to the end of the round: still a round ahead of the
+      // loads it feeds, which are themselves a round ahead of their math)
+      if (key_next + key_step < k_stop) page_seek(walk, key_next + key_step, sk.page_size);
+      ent_next = tbl[walk.pg];
+      lo_next = walk.key_lo;
+    }
 
     // ---- S^T = K Q^T: rows = key (16h + 4grp + r), col = row16 ----
     float sc[8];
@@ -1842,21 +1949,58 @@ int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax
 static void attn_decode_tiled_d128(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                    const at::Tensor& kv_len, at::Tensor& o, at::Tensor& lse,
                                    at::Tensor& ws, double scale, bool causal, int64_t S,
-                                   int64_t chunk);
+                                   int64_t chunk, int64_t Nmax, const at::Tensor* table);
 
+// The paged kernels' K stride argument (see StridesPaged): k is a pool
+// [num_pages, Hkv, page_size, D], table a checked block table.
+static StridesPaged<true> paged_strides_of(const at::Tensor& k, const at::Tensor& table) {
+  StridesPaged<true> s;
+  static_cast<Strides&>(s) = strides_of(k);
+  s.table = table.data_ptr<int>();
+  s.max_pages = (int)table.size(1);
+  s.page_size = (int)k.size(2);
+  s.num_pages = (int)k.size(0);
+  return s;
+}
+
+// What every paged launcher asks of a block table for B batch rows.
+static void check_block_table(const at::Tensor& table, const at::Tensor& q, int64_t B,
+                              const char* who) {
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.device() == q.device() && table.dim() == 2 &&
+                  table.size(0) == B && table.size(1) >= 1 && table.is_contiguous(),
+              who, ": block_table must be int32 [B, max_pages] with max_pages >= 1, contiguous, on "
+                   "q's device");
+}
+
+// block_table none: k, v are the dense cache [B, Hkv, Nmax, D]. With an int32
+// [B, max_pages] table they are page pools [num_pages, Hkv, page_size, D],
+// page_size % 32 == 0, and the capacity max_pages * page_size stands where
+// Nmax stood (splits, workspace, chunking: pass it to the helper functions).
 void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
                        at::Tensor lse, at::Tensor ws, double scale, bool causal,
-                       int64_t num_splits) {
+                       int64_t num_splits, c10::optional<at::Tensor> block_table) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && (q.size(3) == kAttnD || q.size(3) == kAttnD128) &&
                   q.size(2) >= 1 && q.size(0) >= 1 && q.scalar_type() == at::kBFloat16,
               "q must be a bf16 device tensor [B,H,Nq,D] with B, Nq >= 1 and head dim D = 64 or 128");
   const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2), D = q.size(3);
-  TORCH_CHECK(k.dim() == 4 && k.size(0) == B && k.size(3) == D && k.size(1) >= 1 &&
-                  H % k.size(1) == 0 && H >= 1,
-              "k_cache must be [B,Hkv,Nmax,D] with q's B and head dim D and a head count Hkv that "
-              "divides q's: got ", k.sizes(), " for q ", q.sizes());
-  const int64_t Hkv = k.size(1), Nmax = k.size(2), G = H / Hkv;
+  const bool paged = block_table.has_value();
+  TORCH_CHECK(k.dim() == 4 && (paged ? k.size(0) >= 1 : k.size(0) == B) && k.size(3) == D &&
+                  k.size(1) >= 1 && H % k.size(1) == 0 && H >= 1,
+              "k_cache must be [B,Hkv,Nmax,D] (with a block_table: [num_pages,Hkv,page_size,D]) "
+              "with q's B and head dim D and a head count Hkv that divides q's: got ",
+              k.sizes(), " for q ", q.sizes());
+  const int64_t Hkv = k.size(1), G = H / Hkv;
   TORCH_CHECK(v.sizes() == k.sizes(), "v_cache must be shaped like k_cache");
+  int64_t Nmax = k.size(2);
+  if (paged) {
+    check_block_table(*block_table, q, B, "attn_decode_tiled");
+    TORCH_CHECK(k.size(2) >= kKT && k.size(2) % kKT == 0,
+                "attn_decode_tiled: page_size must be a positive multiple of ", kKT, ", got ",
+                k.size(2));
+    TORCH_CHECK(k.size(0) <= INT32_MAX && block_table->size(1) <= INT32_MAX / k.size(2),
+                "attn_decode_tiled: num_pages or max_pages * page_size too large");
+    Nmax = block_table->size(1) * k.size(2);
+  }
   TORCH_CHECK(Nmax >= Nq, "the cache must hold the Nq new rows: Nmax ", Nmax, " < Nq ", Nq);
   TORCH_CHECK(Nmax <= INT32_MAX - 2 * kDecChunkAlign && B * H * Nq <= INT32_MAX / D,
               "attn_decode_tiled: Nmax or B*H*Nq too large");
@@ -1891,17 +2035,24 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
   const int64_t chunk = ceil_div(ceil_div(Nmax, S), kDecChunkAlign) * kDecChunkAlign;
   TORCH_CHECK(B * Hkv * groups * S <= INT32_MAX && S * chunk <= INT32_MAX,
               "attn_decode_tiled: too many blocks or keys");
-  if (D == kAttnD128) return attn_decode_tiled_d128(q, k, v, kv_len, o, lse, ws, scale, causal, S, chunk);
+  const at::Tensor* table = paged ? &*block_table : nullptr;
+  if (D == kAttnD128) {
+    return attn_decode_tiled_d128(q, k, v, kv_len, o, lse, ws, scale, causal, S, chunk, Nmax, table);
+  }
 
   auto stream = c10::hip::getCurrentHIPStream();
   float* ws_o = S > 1 ? ws.data_ptr<float>() : nullptr;
   float* ws_ml = S > 1 ? ws_o + B * Hkv * tiled_tiles(R) * S * kDecPartO : nullptr;
-  hipLaunchKernelGGL(attn_decode_tiled_kernel, dim3((unsigned)(B * Hkv * groups * S)),
-                     dim3(kAttnThreads), 0, stream, (const __hip_bfloat16*)q.data_ptr(),
-                     (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
-                     kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(),
-                     ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax, (int)S, (int)chunk,
-                     (float)scale, causal, strides_of(q), strides_of(k), strides_of(v));
+  auto launch = [&](auto kernel, auto sk) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(B * Hkv * groups * S)), dim3(kAttnThreads), 0,
+                       stream, (const __hip_bfloat16*)q.data_ptr(),
+                       (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
+                       kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(),
+                       lse.data_ptr<float>(), ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax,
+                       (int)S, (int)chunk, (float)scale, causal, strides_of(q), sk, strides_of(v));
+  };
+  if (paged) launch(attn_decode_tiled_kernel<true>, paged_strides_of(k, *table));
+  else launch(attn_decode_tiled_kernel<false>, StridesPaged<false>{strides_of(k)});
   if (S > 1) {
     hipLaunchKernelGGL(attn_decode_tiled_merge_kernel, dim3((unsigned)(B * Hkv * groups)),
                        dim3(kAttnThreads), 0, stream, (const float*)ws_o, (const float*)ws_ml,
@@ -1913,5 +2064,6 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
 
 #include "attention_d128.h"
 #include "attention_decode_d128.h"
+#include "attention_kvcache_append.h"
 
 } // namespace dmlamd

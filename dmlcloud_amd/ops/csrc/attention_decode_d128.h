@@ -16,7 +16,10 @@
 // NaN inside the MFMA, so every key-row index is clamped to len - 1 and the
 // duplicates are masked by the score compare. No atomics: results are bitwise
 // repeatable for a (shape, S). The grid depends on shapes and the device only.
-// Forward only.
+// Forward only. attn_decode_d128_kernel<true> reads k/v as page pools
+// [num_pages, Hkv, page_size, 128] through a block table, with the capacity
+// max_pages * page_size for Nmax (StridesPaged in attention.hip); <false> is
+// the dense code.
 //
 // Work split (decode does ~1 flop per byte, so it is made for bytes in flight):
 //   * the R columns c = g * Nq + i (query head kvh * G + g, row i) of one K/V
@@ -136,12 +139,15 @@ kDecodeFn __device__ __forceinline__ void decode128_store(const Decode128Acc& a,
   if (d4 == 0) lse[row] = kLn2 * a.m + __logf(a.l); // log2 domain -> natural log
 }
 
+// <kPaged>: k and v are page pools read through a block table, Nmax is the
+// capacity max_pages * page_size (see StridesPaged in attention.hip).
+template <bool kPaged>
 kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const int* __restrict__ kv_len,
     __hip_bfloat16* __restrict__ o, float* __restrict__ lse, float* __restrict__ ws_o,
     float* __restrict__ ws_ml, int H, int G, int Nq, int Nmax, int S, int chunk, float scale,
-    bool causal, Strides sq, Strides sk, Strides sv) {
+    bool causal, Strides sq, StridesPaged<kPaged> sk, Strides sv) {
   static_assert(kKT * 64 == kImgElems && kDec128VPieces == 8);
   __shared__ Decode128WaveLds wave_lds[kWavesPerBlock];
   __shared__ __hip_bfloat16 p_lds_all[kWavesPerBlock][kQT][kPStride];
@@ -231,15 +237,17 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_kerne
   const __hip_bfloat16* kp = k + (int64_t)b * sk.b + (int64_t)kvh * sk.h;
   const __hip_bfloat16* vp = v + (int64_t)b * sv.b + (int64_t)kvh * sv.h;
   // K fragments [16-key half h][k-chunk c] and V pieces of the tile at key0,
-  // every row clamped to len - 1
-  auto load_tile = [&](int key0, bf16x8(&kf)[2][kKChunks128],
+  // every row clamped to len - 1. kt / vt: the tile's page_bases() (paged);
+  // the dense code keeps reading its (b, K/V head) slices kp / vp
+  auto load_tile = [&](int key0, const __hip_bfloat16* kt, const __hip_bfloat16* vt,
+                       bf16x8(&kf)[2][kKChunks128],
                        bf16x8(&vpc)[kDec128VPieces]) kDecodeFn __attribute__((always_inline)) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int64_t kr = min(key0 + 16 * h + row16, len - 1);
 #pragma unroll
       for (int c = 0; c < kKChunks128; ++c) {
-        kf[h][c] = *(const bf16x8*)(kp + kr * sk.r + 32 * c + 8 * grp);
+        kf[h][c] = *(const bf16x8*)((kPaged ? kt : kp) + kr * sk.r + 32 * c + 8 * grp);
       }
     }
     // K before V, pinned: loads return in order, so the wait in front of
@@ -250,7 +258,7 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_kerne
 #pragma unroll
     for (int x = 0; x < kDec128VPieces; ++x) {
       const int64_t vr = min(key0 + st_row + 4 * x, len - 1);
-      vpc[x] = *(const bf16x8*)(vp + vr * sv.r + st_col);
+      vpc[x] = *(const bf16x8*)((kPaged ? vt : vp) + vr * sv.r + st_col);
     }
   };
   auto stage_v = [&](int buf, const bf16x8(&vpc)[kDec128VPieces]) kDecodeFn
@@ -271,8 +279,30 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_kerne
   int key0 = k_begin + phase * kKT;
   bool have = key0 < k_stop;
   bf16x8 kf[2][kKChunks128], vpc[kDec128VPieces];
+  // Paged: a walked tile key0 < k_stop <= len lies in an allocated page, index
+  // key0 / page_size <= (len - 1) / page_size < max_pages (len <= capacity),
+  // so only table entries < ceil(len / page_size) are read. Its clamped rows
+  // min(key0 + x, len - 1), x < 32, stay in [key0, key0 + 31]: the same
+  // 32-aligned tile, hence the same page (page_size % 32 == 0), rows
+  // 0..page_size-1 of a page id clamped into the pool. `walk` only ever
+  // seeks to a tile that exists, so the entry it names is one of those.
+  const __hip_bfloat16 *kt = kp, *vt = vp; // paged: the current tile's bases
+  [[maybe_unused]] PageWalk walk = {0, 0};
+  [[maybe_unused]] int ent_next = 0, lo_next = 0; // the NEXT tile's entry and page start
+  [[maybe_unused]] PageTable tbl = nullptr; // block_table[b]
+  if constexpr (kPaged) {
+    if (have) {
+      tbl = (PageTable)(sk.table + (int64_t)b * sk.max_pages);
+      walk.pg = key0 / sk.page_size;
+      walk.key_lo = walk.pg * sk.page_size;
+      page_bases(tbl[walk.pg], walk.key_lo, kvh, k, v, sk, sv, kt, vt);
+      if (key0 + key_step < k_stop) page_seek(walk, key0 + key_step, sk.page_size);
+      ent_next = tbl[walk.pg];
+      lo_next = walk.key_lo;
+    }
+  }
   if (have) {
-    load_tile(key0, kf, vpc);
+    load_tile(key0, kt, vt, kf, vpc);
     stage_v(0, vpc);
   }
   int buf = 0;
@@ -281,7 +311,17 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_kerne
     const int key_next = key0 + key_step;
     const bool has_next = key_next < k_stop;
     bf16x8 kf_next[2][kKChunks128];
-    if (has_next) load_tile(key_next, kf_next, vpc);
+    if constexpr (kPaged) page_bases(ent_next, lo_next, kvh, k, v, sk, sv, kt, vt);
+    if (has_next) load_tile(key_next, kt, vt, kf_next, vpc);
+    if constexpr (kPaged) {
+      // the entry of the tile after next, behind the loads just issued; it
+      // is first used at the top of the next round (the compiler sinks this
+      // scalar load to the end of the round: still a round ahead of the
+      // loads it feeds, which are themselves a round ahead of their math)
+      if (key_next + key_step < k_stop) page_seek(walk, key_next + key_step, sk.page_size);
+      ent_next = tbl[walk.pg];
+      lo_next = walk.key_lo;
+    }
 
     // ---- S^T = K Q^T: rows = key (16h + 4grp + r), col = row16 ----
     float sc[8];
@@ -428,22 +468,27 @@ kDecodeFn __global__ void __launch_bounds__(kAttnThreads) attn_decode_d128_merge
 
 // Launches the pair for arguments attn_decode_tiled has checked; the
 // workspace holds attn_decode_tiled_workspace_floats(B, Hkv, R, S, 128).
+// Nmax is the capacity: k.size(2), or max_pages * page_size with a table.
 static void attn_decode_tiled_d128(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                    const at::Tensor& kv_len, at::Tensor& o, at::Tensor& lse,
                                    at::Tensor& ws, double scale, bool causal, int64_t S,
-                                   int64_t chunk) {
-  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2), Hkv = k.size(1), Nmax = k.size(2);
+                                   int64_t chunk, int64_t Nmax, const at::Tensor* table) {
+  const int64_t B = q.size(0), H = q.size(1), Nq = q.size(2), Hkv = k.size(1);
   const int64_t G = H / Hkv, tiles = ceil_div(G * Nq, kDec128Cols);
   const int64_t groups = ceil_div(tiles, kTileGroup);
   auto stream = c10::hip::getCurrentHIPStream();
   float* ws_o = S > 1 ? ws.data_ptr<float>() : nullptr;
   float* ws_ml = S > 1 ? ws_o + B * Hkv * tiles * S * kDec128PartO : nullptr;
-  hipLaunchKernelGGL(attn_decode_d128_kernel, dim3((unsigned)(B * Hkv * groups * S)),
-                     dim3(kAttnThreads), 0, stream, (const __hip_bfloat16*)q.data_ptr(),
-                     (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
-                     kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(), lse.data_ptr<float>(),
-                     ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax, (int)S, (int)chunk,
-                     (float)scale, causal, strides_of(q), strides_of(k), strides_of(v));
+  auto launch = [&](auto kernel, auto sk) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(B * Hkv * groups * S)), dim3(kAttnThreads), 0,
+                       stream, (const __hip_bfloat16*)q.data_ptr(),
+                       (const __hip_bfloat16*)k.data_ptr(), (const __hip_bfloat16*)v.data_ptr(),
+                       kv_len.data_ptr<int>(), (__hip_bfloat16*)o.data_ptr(),
+                       lse.data_ptr<float>(), ws_o, ws_ml, (int)H, (int)G, (int)Nq, (int)Nmax,
+                       (int)S, (int)chunk, (float)scale, causal, strides_of(q), sk, strides_of(v));
+  };
+  if (table) launch(attn_decode_d128_kernel<true>, paged_strides_of(k, *table));
+  else launch(attn_decode_d128_kernel<false>, StridesPaged<false>{strides_of(k)});
   if (S > 1) {
     hipLaunchKernelGGL(attn_decode_d128_merge_kernel, dim3((unsigned)(B * Hkv * groups)),
                        dim3(kAttnThreads), 0, stream, (const float*)ws_o, (const float*)ws_ml,

@@ -77,7 +77,9 @@ int64_t attn_decode_splits(int64_t B, int64_t Hkv, int64_t Nmax, int64_t num_spl
                            int64_t device);
 void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
                        at::Tensor lse, at::Tensor ws, double scale, bool causal,
-                       int64_t num_splits);
+                       int64_t num_splits, c10::optional<at::Tensor> block_table);
+void kvcache_append(at::Tensor k_new, at::Tensor v_new, at::Tensor k_cache, at::Tensor v_cache,
+                    at::Tensor kv_len, c10::optional<at::Tensor> block_table);
 int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, int64_t S,
                                            int64_t D);
 int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax,
@@ -146,9 +148,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_tiled", &dmlamd::attn_decode_tiled,
         "Tiled split-KV attention over a K/V cache for any R = (H/Hkv)*Nq >= 1 columns per K/V "
         "head: 16-column MFMA tiles, up to four per block (MFMA bf16, D=64 or 128 by q's last "
-        "dim; num_splits 0 = auto)",
+        "dim; num_splits 0 = auto). With an int32 block_table [B, max_pages] the caches are page "
+        "pools [num_pages, Hkv, page_size, D], page_size % 32 == 0, and max_pages * page_size "
+        "stands for Nmax",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"), py::arg("o"),
-        py::arg("lse"), py::arg("ws"), py::arg("scale"), py::arg("causal"), py::arg("num_splits"));
+        py::arg("lse"), py::arg("ws"), py::arg("scale"), py::arg("causal"), py::arg("num_splits"),
+        py::arg("block_table") = py::none());
+  m.def("kvcache_append", &dmlamd::kvcache_append,
+        "Write k_new / v_new [B, Hkv, Nq, D] into a dense [B, Hkv, Nmax, D] or, with a block_table, "
+        "paged [num_pages, Hkv, page_size, D] K/V cache at the positions sdpa_kvcache gives the "
+        "same rows (kv_len already counts them); one launch, no host sync",
+        py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("kv_len"), py::arg("block_table") = py::none());
   m.def("attn_decode_tiled_workspace_floats", &dmlamd::attn_decode_tiled_workspace_floats,
         "fp32 elements attn_decode_tiled's workspace needs for R columns, S splits and head dim D",
         py::arg("B"), py::arg("Hkv"), py::arg("R"), py::arg("S"), py::arg("D") = 64);

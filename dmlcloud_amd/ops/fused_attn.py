@@ -51,6 +51,16 @@ whose behaviour for kv length != q length (torch SDPA, top-left causal)
 is unchanged. Verified in tests/test_gpu_attention_kvcache.py,
 tests/test_gpu_attention_kvcache_tiled.py and
 tests/test_gpu_attention_kvcache_d128.py.
+
+Paged cache: `sdpa_kvcache(..., block_table=t)` reads K and V from page
+pools [num_pages, Hkv, page_size, D] through an integer [B, max_pages] block
+table (page_size a multiple of 32: the paged instantiations of the tiled
+kernels, one scalar table read per 32-key tile; other page sizes: the torch
+reference), and `kvcache_append(k_new, v_new, k_cache, v_cache, kv_len,
+block_table=None)` writes the new tokens' K/V rows into a dense or paged
+cache in one launch, positions resolved on the device
+(ops/csrc/attention_kvcache_append.h). Verified in
+tests/test_gpu_attention_kvcache_paged.py.
 """
 
 import math
@@ -248,22 +258,20 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
     return F.scaled_dot_product_attention(q, k, v, attn_mask=document_mask(doc_start, causal), **gqa)
 
 
-def _kvcache_usable(q, k_cache, v_cache, kv_len):
+def _kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None):
     if not fused_attention_enabled():
         return False
-    return (
+    ok = (
         q.is_cuda
         and is_available()
         and q.dtype == torch.bfloat16
         and q.dim() == 4
         and q.shape[-1] in (64, 128)
         and k_cache.dim() == 4
-        and k_cache.shape[0] == q.shape[0]
         and k_cache.shape[3] == q.shape[-1]
         and k_cache.shape[1] >= 1
         and q.shape[1] % k_cache.shape[1] == 0
         and (q.shape[1] // k_cache.shape[1]) * q.shape[2] >= 1
-        and k_cache.shape[2] >= q.shape[2]
         and v_cache.shape == k_cache.shape
         and k_cache.dtype == q.dtype
         and v_cache.dtype == q.dtype
@@ -274,16 +282,33 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len):
         and kv_len.shape == (q.shape[0],)
         and kv_len.device == q.device
     )
+    if block_table is None:
+        return ok and k_cache.shape[0] == q.shape[0] and k_cache.shape[2] >= q.shape[2]
+    return (
+        ok
+        and k_cache.shape[0] >= 1
+        and k_cache.shape[2] >= 32
+        and k_cache.shape[2] % 32 == 0
+        and block_table.dtype in _INT_DTYPES
+        and block_table.dim() == 2
+        and block_table.shape[0] == q.shape[0]
+        and block_table.shape[1] >= 1
+        and block_table.device == q.device
+        and block_table.shape[1] * k_cache.shape[2] >= q.shape[2]
+    )
 
 
-def fused_kvcache_usable(q, k_cache, v_cache, kv_len) -> bool:
-    """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len)` will run the
-    native split-KV kernels, False when it will run the pure-torch
-    reference: bf16 device tensors, q [B, H, Nq, D] with D = 64 or 128 and
-    any Nq >= 1, caches [B, Hkv, Nmax, D] with Hkv dividing H, Nmax >= Nq, last dims
-    contiguous, an integer [B] kv_len on q's device,
-    extension built, no DMLCLOUD_DISABLE_FUSED_ATTN."""
-    return bool(_kvcache_usable(q, k_cache, v_cache, kv_len))
+def fused_kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None) -> bool:
+    """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len, block_table=...)`
+    will run the native split-KV kernels, False when it will run the
+    pure-torch reference: bf16 device tensors, q [B, H, Nq, D] with D = 64 or
+    128 and any Nq >= 1, last dims contiguous, an integer [B] kv_len on q's
+    device, extension built, no DMLCLOUD_DISABLE_FUSED_ATTN, and
+    without a table caches [B, Hkv, Nmax, D] with Hkv dividing H and
+    Nmax >= Nq; with one, pools [num_pages, Hkv, page_size, D] with Hkv
+    dividing H and page_size a positive multiple of 32, and an integer
+    [B, max_pages] table on q's device with max_pages * page_size >= Nq."""
+    return bool(_kvcache_usable(q, k_cache, v_cache, kv_len, block_table))
 
 
 def _vector_loadable(t):
@@ -291,7 +316,9 @@ def _vector_loadable(t):
     return t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1])
 
 
-def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: int = 0, return_lse: bool = False):
+def sdpa_kvcache(
+    q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: int = 0, return_lse: bool = False, block_table=None
+):
     """Attention of new query rows over a partly filled K/V cache: one row
     (decoding), a few (speculative verification) or a whole chunk of a
     prompt (chunked prefill, continuation); forward only.
@@ -306,41 +333,56 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     at or past kv_len[b] are never read. The value used for kv_len[b] is
     clamped to [Nq, Nmax] (causal) or [1, Nmax].
 
+    Paged cache: with an integer `block_table` [B, max_pages] on q's device,
+    k_cache and v_cache are page POOLS [num_pages, Hkv, page_size, D] and
+    logical key j of batch row b is row j % page_size of page
+    block_table[b, j // page_size]. The capacity max_pages * page_size stands
+    wherever Nmax stands above. Only the entries below
+    ceil(kv_len[b] / page_size) are read, later ones may hold anything; an
+    entry that is read is clamped to [0, num_pages - 1].
+
     On the native path (`fused_kvcache_usable`) the lengths are read on the
     device: no host sync, hipGraph-capturable, and kv_len and the cache
-    contents may change between replays. The keys are split over
-    `num_splits` blocks per (b, K/V head), 0 = chosen from the shapes and
-    the device's CU count, and merged by a second kernel; any batch / head /
-    row strides pass without a copy ([B, Nmax, Hkv, D] memory viewed
-    transposed included). R = (H / Hkv) * Nq query columns share a K/V
-    head. D = 64: R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16
-    the tiled ones (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four
-    per block, key tiles past a tile's last causal position skipped). D = 128
-    has one kernel pair of the tiled form for every R
-    (ops/csrc/attention_decode_d128.h), reached through
-    `_C.attn_decode_tiled` as well. Everything else (other head dims, other
-    dtypes) runs `_attention_ref.kvcache_attention_ref`.
+    contents (and the block table) may change between replays. The keys are
+    split over `num_splits` blocks per (b, K/V head), 0 = chosen from the
+    shapes and the device's CU count, and merged by a second kernel; any
+    batch (page) / head / row strides pass without a copy ([B, Nmax, Hkv, D]
+    or [num_pages, page_size, Hkv, D] memory viewed transposed included).
+    R = (H / Hkv) * Nq query columns share a K/V head. Without a table, D = 64:
+    R <= 16 runs the decode kernels (`_C.attn_decode`), R > 16 the tiled ones
+    (`_C.attn_decode_tiled`: 16-column MFMA tiles, up to four per block, key
+    tiles past a tile's last causal position skipped); D = 128 has one kernel
+    pair of the tiled form for every R (ops/csrc/attention_decode_d128.h),
+    reached through `_C.attn_decode_tiled` as well. With a table whose
+    page_size is a multiple of 32, every R and both D run the paged
+    instantiations of the tiled kernels (`_C.attn_decode_tiled(...,
+    block_table)`). Everything else (other head dims, other dtypes, other page
+    sizes) runs `_attention_ref.kvcache_attention_ref`.
 
     Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
     lse [B, H, Nq] fp32."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k_cache, v_cache)):
         raise RuntimeError('sdpa_kvcache is forward only: call it under torch.no_grad() or detach its inputs')
-    if not _kvcache_usable(q, k_cache, v_cache, kv_len):
+    if not _kvcache_usable(q, k_cache, v_cache, kv_len, block_table):
         from ._attention_ref import kvcache_attention_ref
 
-        return kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal, return_lse)
+        return kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal, return_lse, block_table)
     B, H, Nq, D = q.shape
     Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
     q, k_cache, v_cache = (t if _vector_loadable(t) else t.contiguous() for t in (q, k_cache, v_cache))
     kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
     R = (H // Hkv) * Nq
-    if R > 16 or D == 128:
+    if block_table is not None:
+        if block_table.dtype != torch.int32 or not block_table.is_contiguous():
+            block_table = block_table.detach().to(torch.int32).contiguous()
+        Nmax = block_table.shape[1] * k_cache.shape[2]  # the capacity
+    if block_table is not None or R > 16 or D == 128:
         splits = _C.attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device())
         o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
         lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
         # one partial per (column tile, split); every element the merge reads is written
         ws = torch.empty(_C.attn_decode_tiled_workspace_floats(B, Hkv, R, splits, D), dtype=torch.float32, device=q.device)
-        _C.attn_decode_tiled(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits)
+        _C.attn_decode_tiled(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits, block_table)
         return (o, lse) if return_lse else o
     splits = _C.attn_decode_splits(B, Hkv, Nmax, num_splits, q.get_device())
     o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
@@ -349,6 +391,55 @@ def sdpa_kvcache(q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: i
     ws = torch.empty(_C.attn_decode_workspace_floats(B, Hkv, splits), dtype=torch.float32, device=q.device)
     _C.attn_decode(q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits)
     return (o, lse) if return_lse else o
+
+
+def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
+    """Write the K and V rows of Nq new tokens per batch row into a K/V cache,
+    in place, at the positions `sdpa_kvcache` gives the same query rows.
+
+    k_new, v_new are [B, Hkv, Nq, D] (strided views of a qkv projection
+    pass). kv_len, integer [B], ALREADY counts the new rows, as in
+    `sdpa_kvcache`: row i of batch row b goes to logical position
+    clamp(kv_len[b], Nq, capacity) - Nq + i. Without a table the caches are
+    [B, Hkv, Nmax, D], capacity = Nmax, and that is cache row (b, :, pos).
+    With an integer `block_table` [B, max_pages] they are page pools
+    [num_pages, Hkv, page_size, D], any page_size >= 1, capacity = max_pages *
+    page_size, and it is row pos % page_size of page
+    block_table[b, pos // page_size], the entry clamped to [0, num_pages - 1].
+    No other cache row is written.
+
+    Native path (`_C.kvcache_append`, one launch for K and V, positions
+    resolved on the device: no host sync, hipGraph-capturable): all five
+    tensors bf16 (kv_len and the table integer) on one device, D = 64 or 128,
+    last dims contiguous, the caches 16-byte loadable (base and strides
+    multiples of 8 elements; they are written in place and cannot be copied),
+    extension built, no DMLCLOUD_DISABLE_FUSED_ATTN. k_new / v_new that are not
+    16-byte loadable are copied first. Everything else runs
+    `_attention_ref.kvcache_append_ref`, two index writes."""
+    tensors = (k_new, v_new, k_cache, v_cache)
+    native = (
+        fused_attention_enabled()
+        and k_new.is_cuda
+        and is_available()
+        and k_new.dim() == 4
+        and k_cache.dim() == 4
+        and k_new.shape[-1] in (64, 128)
+        and all(t.dtype == torch.bfloat16 and t.device == k_new.device and t.stride(-1) == 1 for t in tensors)
+        and _vector_loadable(k_cache)
+        and _vector_loadable(v_cache)
+        and kv_len.dtype in _INT_DTYPES
+        and kv_len.device == k_new.device
+        and (block_table is None or (block_table.dtype in _INT_DTYPES and block_table.device == k_new.device))
+    )
+    if not native:
+        from ._attention_ref import kvcache_append_ref
+
+        return kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table)
+    k_new, v_new = (t if _vector_loadable(t) else t.contiguous() for t in (k_new, v_new))
+    kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
+    if block_table is not None and (block_table.dtype != torch.int32 or not block_table.is_contiguous()):
+        block_table = block_table.detach().to(torch.int32).contiguous()
+    _C.kvcache_append(k_new.detach(), v_new.detach(), k_cache, v_cache, kv_len, block_table)
 
 
 def fused_attention_enabled() -> bool:

@@ -25,7 +25,9 @@ a K/V cache from an 8-token prompt and decodes through
 ops.fused_attn.sdpa_kvcache (the split-KV decode kernels on the device).
 --prefill-chunk C feeds that prompt to the cache C tokens at a time through
 GPT2.extend instead (the tiled KV-cache kernels once a chunk has more than
-16 query columns per K/V head).
+16 query columns per K/V head). --page-size P keeps the cache in pages of P
+rows read through a block table (GPT2.init_paged_cache; the paged kernels
+for P a multiple of 32).
 """
 
 import argparse
@@ -156,6 +158,9 @@ def main():
     parser.add_argument(
         '--prefill-chunk', type=int, default=None, metavar='C', help='with --sample: prefill the prompt C tokens at a time'
     )
+    parser.add_argument(
+        '--page-size', type=int, default=None, metavar='P', help='with --sample: a paged K/V cache with pages of P rows'
+    )
     args = parser.parse_args()
 
     init_process_group_auto()
@@ -165,7 +170,7 @@ def main():
     if args.sample > 0 and torch.distributed.get_rank() == 0:
         model = pipeline.models['gpt2'].module
         prompt = torch.arange(1, 9, device=next(model.parameters()).device).unsqueeze(0)
-        out = model.generate(prompt, args.sample, prefill_chunk=args.prefill_chunk)
+        out = model.generate(prompt, args.sample, prefill_chunk=args.prefill_chunk, page_size=args.page_size)
         print('sampled tokens:', out[0, 8:].tolist())
 
 

@@ -12,6 +12,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py --decode   # KV-cache decode (sdpa_kvcache) alone
     python tools/bench_attn.py --decode-tiled   # sdpa_kvcache, more than 16 columns
     python tools/bench_attn.py --decode-d128    # sdpa_kvcache at head dim 128
+    python tools/bench_attn.py --decode-paged   # paged cache against dense; kvcache_append
     python tools/bench_attn.py --d128     # head dim 128: native against the torch SDPA fallback
 """
 
@@ -316,6 +317,92 @@ def main_decode_d128():
         bench_decode_d128(1, 8, 8, 512, 4096)
 
 
+def _spread(ts):
+    ts = sorted(ts)
+    return f'{ts[len(ts) // 2]:7.1f}us [{ts[0]:.1f}..{ts[-1]:.1f}]'
+
+
+def bench_decode_paged(b, h, hkv, nq, nmax, d, rounds=3):
+    """Nq new causal rows over a FULL cache of nmax keys: the dense native
+    path | the paged kernels at page_size 64 | at 256, pages shuffled over
+    the pool; the three alternate over `rounds` rounds in one process.
+    Median and min..max per cell."""
+    from dmlcloud_amd.ops.fused_attn import fused_kvcache_usable, sdpa_kvcache
+
+    torch.manual_seed(0)
+    mk = lambda heads, n: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    q, k, v = mk(h, nq), mk(hkv, nmax), mk(hkv, nmax)
+    kv_len = torch.full((b,), nmax, dtype=torch.int32, device=DEV)
+    fns = {'dense': lambda: sdpa_kvcache(q, k, v, kv_len)}
+    for ps in (64, 256):
+        n = b * nmax // ps
+        table = torch.randperm(n, device=DEV).to(torch.int32).view(b, nmax // ps)
+        pools = []
+        for t in (k, v):  # page table[b, p] holds rows p * ps .. of batch row b
+            pool = torch.empty(n, hkv, ps, d, dtype=t.dtype, device=DEV)
+            pool[table.long().view(-1)] = t.view(b, hkv, nmax // ps, ps, d).transpose(1, 2).reshape(n, hkv, ps, d)
+            pools.append(pool)
+        assert fused_kvcache_usable(q, *pools, kv_len, table)
+        fns[f'paged {ps}'] = lambda pools=pools, table=table: sdpa_kvcache(q, *pools, kv_len, block_table=table)
+    with torch.no_grad():
+        want = fns['dense']()
+        assert all(torch.equal(fn(), want) for fn in fns.values()), 'paged and dense outputs differ'
+        times = {name: [] for name in fns}
+        for _ in range(rounds):
+            for name, fn in fns.items():
+                times[name].append(time_fn(fn, reps=200, warmup=20))
+    print(
+        f'DECODE-PAGED D={d} B={b} H={h} Hkv={hkv} Nq={nq} Nmax={nmax}: '
+        + ' | '.join(f'{name} {_spread(ts)}' for name, ts in times.items()),
+        flush=True,
+    )
+
+
+def bench_append(b, hkv, nq, d, nmax=1024, rounds=3):
+    """One kvcache_append (dense cache, and paged at page_size 64) against the
+    two index_put calls of CausalSelfAttention.decode / extend, new rows
+    taken as strided views of a qkv projection, alternated."""
+    from dmlcloud_amd.ops.fused_attn import kvcache_append
+
+    torch.manual_seed(0)
+    qkv = torch.randn(b, nq, 3 * hkv * d, device=DEV).to(torch.bfloat16)
+    k_new, v_new = (t.view(b, nq, hkv, d).transpose(1, 2) for t in qkv.split(hkv * d, dim=2)[1:])
+    k, v = (torch.zeros(b, hkv, nmax, d, dtype=torch.bfloat16, device=DEV) for _ in range(2))
+    kp, vp = (t.view(b * nmax // 64, hkv, 64, d) for t in (torch.zeros_like(k), torch.zeros_like(v)))
+    table = torch.randperm(b * nmax // 64, device=DEV).to(torch.int32).view(b, nmax // 64)
+    kv_len = torch.full((b,), 512 + nq, dtype=torch.int32, device=DEV)
+    rows = (kv_len.long() - nq).unsqueeze(1) + torch.arange(nq, device=DEV)
+    batch = torch.arange(b, device=DEV).unsqueeze(1)
+
+    def index_put():
+        k[batch, :, rows] = k_new.transpose(1, 2)
+        v[batch, :, rows] = v_new.transpose(1, 2)
+
+    fns = {
+        'two index_put': index_put,
+        'kvcache_append dense': lambda: kvcache_append(k_new, v_new, k, v, kv_len),
+        'kvcache_append paged 64': lambda: kvcache_append(k_new, v_new, kp, vp, kv_len, table),
+    }
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            times[name].append(time_fn(fn, reps=200, warmup=20))
+    print(
+        f'APPEND B={b} Hkv={hkv} Nq={nq} D={d}: ' + ' | '.join(f'{name} {_spread(ts)}' for name, ts in times.items()),
+        flush=True,
+    )
+
+
+def main_decode_paged():
+    bench_decode_paged(8, 12, 12, 1, 1024, 64)
+    bench_decode_paged(8, 32, 8, 1, 4096, 64)
+    bench_decode_paged(1, 12, 12, 512, 4096, 64)
+    bench_decode_paged(8, 6, 6, 1, 4096, 128)
+    bench_decode_paged(1, 8, 8, 512, 4096, 128)
+    bench_append(64, 12, 1, 64)
+    bench_append(8, 12, 256, 64)
+
+
 def main_gqa():
     bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
     bench_gqa(64, 12, 1, 1024)  # ... and as MQA
@@ -383,6 +470,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if '--decode-d128' in sys.argv[1:]:
         main_decode_d128()
+        sys.exit(0)
+    if '--decode-paged' in sys.argv[1:]:
+        main_decode_paged()
         sys.exit(0)
     if '--decode' in sys.argv[1:]:
         main_decode()
