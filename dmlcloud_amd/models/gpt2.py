@@ -33,6 +33,14 @@ in pools of fixed-size pages named by a per-row block table
 rows are written by `ops.fused_attn.kvcache_append` (one launch per layer)
 and read by `sdpa_kvcache(block_table=...)`. The table is fixed when the
 cache is made; a free list or growth is the caller's.
+
+FP8 cache: `init_cache(dtype=torch.float8_e4m3fn)`, `init_paged_cache(dtype=
+...)` or `generate(kv_dtype=...)` keep K and V as e4m3 bytes with per-layer,
+per-K/V-head fp32 scales (`cache.k_scale[layer]`, `cache.v_scale[layer]`,
+[n_kv_head], ones by default, assignable; calibration is the caller's). Every
+write then goes through `kvcache_append`, which quantises, dense cache
+included, and every read through `sdpa_kvcache(k_scale=, v_scale=)`; `prefill`
+still attends the prompt's own unquantised K/V.
 """
 
 import math
@@ -125,22 +133,26 @@ class CausalSelfAttention(nn.Module):
         y = sdpa_kvcache(q, k_cache, v_cache, kv_len, causal=True)
         return self.c_proj(y.transpose(1, 2).reshape(B, T, C))
 
-    def prefill_paged(self, x, k_pool, v_pool, kv_len, block_table):
+    def prefill_paged(self, x, k_pool, v_pool, kv_len, block_table, k_scale=None, v_scale=None):
         """forward(x) that also writes the prompt's K/V through the block
-        table (kv_len already holds T for every row)."""
+        table (kv_len already holds T for every row). block_table None: a
+        dense fp8 cache, which is written by the same launch."""
         B, T, C = x.shape
         q, k, v = self._heads(x)
-        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table)
+        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table, k_scale=k_scale, v_scale=v_scale)
         return self.c_proj(sdpa(q, k, v, causal=True).transpose(1, 2).reshape(B, T, C))
 
-    def extend_paged(self, x, k_pool, v_pool, kv_len, block_table):
+    def extend_paged(self, x, k_pool, v_pool, kv_len, block_table, k_scale=None, v_scale=None):
         """T >= 1 new tokens per row, x [B, T, C], on a paged cache: their K/V
         go to logical rows kv_len[b] - T + t of the row's pages (one launch),
-        then token t attends logical rows 0..kv_len[b] - T + t."""
+        then token t attends logical rows 0..kv_len[b] - T + t. block_table
+        None: a dense fp8 cache, the same two calls."""
         B, T, C = x.shape
         q, k, v = self._heads(x)
-        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table)
-        y = sdpa_kvcache(q, k_pool, v_pool, kv_len, causal=True, block_table=block_table)
+        kvcache_append(k, v, k_pool, v_pool, kv_len, block_table, k_scale=k_scale, v_scale=v_scale)
+        y = sdpa_kvcache(
+            q, k_pool, v_pool, kv_len, causal=True, block_table=block_table, k_scale=k_scale, v_scale=v_scale
+        )
         return self.c_proj(y.transpose(1, 2).reshape(B, T, C))
 
 
@@ -185,11 +197,15 @@ class Block(nn.Module):
 @dataclass
 class KVCache:
     """Per-layer K and V, [B, n_kv_head, max_len, head_dim] each, and the
-    number of valid rows of every batch row, int32 [B] on the device."""
+    number of valid rows of every batch row, int32 [B] on the device. An fp8
+    (float8_e4m3fn) cache also carries per-layer fp32 [n_kv_head] scales;
+    they stay None for every other dtype."""
 
     k: List[torch.Tensor]
     v: List[torch.Tensor]
     kv_len: torch.Tensor
+    k_scale: Optional[List[torch.Tensor]] = None
+    v_scale: Optional[List[torch.Tensor]] = None
 
 
 @dataclass
@@ -198,13 +214,16 @@ class PagedKVCache:
     head_dim] each; the number of valid rows of every batch row, int32 [B];
     and the block table, int32 [B, max_pages]: logical row j of batch row b
     is row j % page_size of page block_table[b, j // page_size]. All on the
-    device."""
+    device. An fp8 (float8_e4m3fn) cache also carries per-layer fp32
+    [n_kv_head] scales; they stay None for every other dtype."""
 
     k: List[torch.Tensor]
     v: List[torch.Tensor]
     kv_len: torch.Tensor
     block_table: torch.Tensor
     page_size: int
+    k_scale: Optional[List[torch.Tensor]] = None
+    v_scale: Optional[List[torch.Tensor]] = None
 
 
 class GPT2(nn.Module):
@@ -255,17 +274,29 @@ class GPT2(nn.Module):
         loss = cross_entropy(logits.view(-1, logits.size(-1)), targets.reshape(-1))
         return logits, loss
 
+    def _init_scales(self, dtype, n_kv_head, device):
+        # per-layer K and V scales of an fp8 cache, ones; (None, None) otherwise
+        if dtype != torch.float8_e4m3fn:
+            return None, None
+        n_layer = self.cfg.n_layer
+        k_scale, v_scale = ([torch.ones(n_kv_head, device=device) for _ in range(n_layer)] for _ in range(2))
+        return k_scale, v_scale
+
     def init_cache(self, batch, max_len, device=None, dtype=None) -> KVCache:
-        """An empty cache for `batch` rows of up to `max_len` tokens."""
+        """An empty cache for `batch` rows of up to `max_len` tokens.
+        dtype=torch.float8_e4m3fn makes it an fp8 cache with unit scales."""
         cfg = self.cfg
         device = self.wte.weight.device if device is None else device
         dtype = self.wte.weight.dtype if dtype is None else dtype
         n_kv_head = cfg.n_head if cfg.n_kv_head is None else cfg.n_kv_head
         shape = (batch, n_kv_head, max_len, cfg.n_embd // cfg.n_head)
+        k_scale, v_scale = self._init_scales(dtype, n_kv_head, device)
         return KVCache(
             k=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
             v=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
             kv_len=torch.zeros(batch, dtype=torch.int32, device=device),
+            k_scale=k_scale,
+            v_scale=v_scale,
         )
 
     def init_paged_cache(
@@ -275,7 +306,8 @@ class GPT2(nn.Module):
         ceil(max_len / page_size) table entries per row over pools of
         `num_pages` pages (default: one page per entry). The default table
         hands the pages out in order; any integer [batch, max_pages] table
-        whose live entries name distinct pages may be passed instead."""
+        whose live entries name distinct pages may be passed instead.
+        dtype=torch.float8_e4m3fn makes it an fp8 cache with unit scales."""
         cfg = self.cfg
         device = self.wte.weight.device if device is None else device
         dtype = self.wte.weight.dtype if dtype is None else dtype
@@ -288,12 +320,15 @@ class GPT2(nn.Module):
             block_table = block_table.to(device=device, dtype=torch.int32).contiguous()
         num_pages = batch * max_pages if num_pages is None else num_pages
         shape = (num_pages, n_kv_head, page_size, cfg.n_embd // cfg.n_head)
+        k_scale, v_scale = self._init_scales(dtype, n_kv_head, device)
         return PagedKVCache(
             k=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
             v=[torch.empty(shape, device=device, dtype=dtype) for _ in range(cfg.n_layer)],
             kv_len=torch.zeros(batch, dtype=torch.int32, device=device),
             block_table=block_table,
             page_size=page_size,
+            k_scale=k_scale,
+            v_scale=v_scale,
         )
 
     @torch.no_grad()
@@ -303,24 +338,38 @@ class GPT2(nn.Module):
         position's logits [B, vocab]."""
         B, T = idx.shape
         x = self.wte(idx) + self.wpe(torch.arange(T, device=idx.device))
-        if isinstance(cache, PagedKVCache):
+        if self._appends(cache):
             cache.kv_len.fill_(T)
-            for block, k_pool, v_pool in zip(self.blocks, cache.k, cache.v):
-                x = block.prefill_paged(x, k_pool, v_pool, cache.kv_len, cache.block_table)
+            for block, args in zip(self.blocks, self._append_args(cache)):
+                x = block.prefill_paged(x, *args)
             return self.lm_head(self.ln_f(x[:, -1]))
         for block, k_cache, v_cache in zip(self.blocks, cache.k, cache.v):
             x = block.prefill(x, k_cache, v_cache)
         cache.kv_len.fill_(T)
         return self.lm_head(self.ln_f(x[:, -1]))
 
-    def _extend_paged(self, idx, cache: PagedKVCache):
+    @staticmethod
+    def _appends(cache):
+        """True when the cache is written by `kvcache_append`: paged caches,
+        and dense fp8 ones (index writes cannot quantise)."""
+        return isinstance(cache, PagedKVCache) or cache.k_scale is not None
+
+    @staticmethod
+    def _append_args(cache):
+        """Per layer: (k, v, kv_len, block_table or None, k_scale, v_scale)."""
+        table = cache.block_table if isinstance(cache, PagedKVCache) else None
+        none = [None] * len(cache.k)
+        for k, v, ks, vs in zip(cache.k, cache.v, cache.k_scale or none, cache.v_scale or none):
+            yield k, v, cache.kv_len, table, ks, vs
+
+    def _extend_paged(self, idx, cache):
         B, T = idx.shape
         rows = cache.kv_len.long().unsqueeze(1) + torch.arange(T, device=idx.device)  # before the increment
         cache.kv_len += T
         x = self.wte(idx) + self.wpe(rows.clamp(max=self.cfg.n_positions - 1))
-        for block, k_pool, v_pool in zip(self.blocks, cache.k, cache.v):
+        for block, args in zip(self.blocks, self._append_args(cache)):
             # (a full cache overwrites its last rows instead of writing past them)
-            x = block.extend_paged(x, k_pool, v_pool, cache.kv_len, cache.block_table)
+            x = block.extend_paged(x, *args)
         return self.lm_head(self.ln_f(x[:, -1]))
 
     @torch.no_grad()
@@ -329,7 +378,7 @@ class GPT2(nn.Module):
         and return the logits [B, vocab] for the token after it. Positions
         come from cache.kv_len on the device; nothing is read back."""
         B = tokens.shape[0]
-        if isinstance(cache, PagedKVCache):
+        if self._appends(cache):
             return self._extend_paged(tokens.view(B, 1), cache)
         pos = cache.kv_len.long()  # the new token's row, before the increment
         cache.kv_len += 1
@@ -349,7 +398,7 @@ class GPT2(nn.Module):
         nothing is read back. Attention runs through sdpa_kvcache with
         Nq = T."""
         B, T = idx.shape
-        if isinstance(cache, PagedKVCache):
+        if self._appends(cache):
             return self._extend_paged(idx, cache)
         rows = cache.kv_len.long().unsqueeze(1) + torch.arange(T, device=idx.device)  # [B, T], before the increment
         cache.kv_len += T
@@ -361,19 +410,23 @@ class GPT2(nn.Module):
         return self.lm_head(self.ln_f(x[:, -1]))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=0.0, generator=None, prefill_chunk=None, page_size=None):
+    def generate(
+        self, idx, max_new_tokens, temperature=0.0, generator=None, prefill_chunk=None, page_size=None, kv_dtype=None
+    ):
         """idx [B, T] followed by max_new_tokens sampled tokens,
         [B, T + max_new_tokens]. temperature = 0 is greedy; otherwise the
         next token is drawn from softmax(logits / temperature). The prompt
         runs through `prefill` in one piece, or with prefill_chunk = c >= 1
         through `extend` in pieces of at most c tokens. page_size = p keeps
-        the K/V cache in pages of p rows (`init_paged_cache`)."""
+        the K/V cache in pages of p rows (`init_paged_cache`). kv_dtype is
+        the cache's dtype (None: the weights'; torch.float8_e4m3fn: an fp8
+        cache with unit scales)."""
         B, T = idx.shape
         assert T >= 1 and T + max_new_tokens <= self.cfg.n_positions, 'sequence exceeds n_positions'
         if page_size is None:
-            cache = self.init_cache(B, T + max_new_tokens)
+            cache = self.init_cache(B, T + max_new_tokens, dtype=kv_dtype)
         else:
-            cache = self.init_paged_cache(B, T + max_new_tokens, page_size)
+            cache = self.init_paged_cache(B, T + max_new_tokens, page_size, dtype=kv_dtype)
         out = [idx]
         if prefill_chunk is None:
             logits = self.prefill(idx, cache)

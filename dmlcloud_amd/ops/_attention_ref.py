@@ -450,15 +450,46 @@ def gather_pages(pool, block_table):
     return pages.transpose(1, 2).reshape(B, Hkv, max_pages * page_size, D)
 
 
-def kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
+_FP8 = torch.float8_e4m3fn
+_FP8_MAX = 448.0  # the largest finite e4m3fn value
+
+
+def _check_fp8_scales(k_cache, v_cache, k_scale, v_scale):
+    """True for an e4m3 cache pair; a scale with any other cache is an error."""
+    fp8 = k_cache.dtype == _FP8 and v_cache.dtype == _FP8
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError('k_scale / v_scale go with float8_e4m3fn caches only')
+    return fp8
+
+
+def quantize_fp8(x, scale=None):
+    """The e4m3 bytes `kvcache_append` stores for rows x [B, Hkv, Nq, D] and a
+    per-head fp32 scale [Hkv] (None = ones):
+    e4m3_rne(clamp(float(x) / scale[h], -448, 448)), a true fp32 division."""
+    xf = x.float()
+    if scale is not None:
+        xf = xf / scale.float().view(1, -1, 1, 1)
+    return xf.clamp(-_FP8_MAX, _FP8_MAX).to(_FP8)
+
+
+def dequantize_fp8(cache, scale=None):
+    """fp32 rows of an e4m3 cache [.., Hkv, rows, D]: float(byte) * scale[h]."""
+    cf = cache.float()
+    return cf if scale is None else cf * scale.float().view(1, -1, 1, 1)
+
+
+def kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table=None, k_scale=None, v_scale=None):
     """Index writes of `ops.fused_attn.kvcache_append`: row i of batch row b
     goes to logical position clamp(kv_len[b], Nq, capacity) - Nq + i, which is
     cache row (b, :, pos) without a table and row pos % page_size of page
-    block_table[b, pos // page_size] (clamped to the pool) with one."""
+    block_table[b, pos // page_size] (clamped to the pool) with one. A
+    float8_e4m3fn cache stores `quantize_fp8(rows, scale)`; the bytes move as
+    uint8 (index writes of fp8 tensors are not everywhere implemented)."""
     B, Hkv, Nq, D = k_new.shape
     page_size = k_cache.shape[2]
     capacity = page_size * (1 if block_table is None else block_table.shape[1])
     assert capacity >= Nq and v_cache.shape == k_cache.shape and v_new.shape == k_new.shape
+    fp8 = _check_fp8_scales(k_cache, v_cache, k_scale, v_scale)
     ln = kv_len.long().clamp(Nq, capacity)
     pos = ln[:, None] - Nq + torch.arange(Nq, device=k_new.device)[None, :]  # [B, Nq]
     if block_table is None:
@@ -466,12 +497,18 @@ def kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table=None)
     else:
         page = block_table.long().gather(1, pos // page_size).clamp(0, k_cache.shape[0] - 1)
         row = pos % page_size
+    if fp8:
+        k_cache.view(torch.uint8)[page, :, row] = quantize_fp8(k_new, k_scale).view(torch.uint8).transpose(1, 2)
+        v_cache.view(torch.uint8)[page, :, row] = quantize_fp8(v_new, v_scale).view(torch.uint8).transpose(1, 2)
+        return
     # index result [B, Nq, Hkv, D]
     k_cache[page, :, row] = k_new.transpose(1, 2).to(k_cache.dtype)
     v_cache[page, :, row] = v_new.transpose(1, 2).to(v_cache.dtype)
 
 
-def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=False, block_table=None):
+def kvcache_attention_ref(
+    q, k_cache, v_cache, kv_len, causal=True, return_lse=False, block_table=None, k_scale=None, v_scale=None
+):
     """fp32 masked softmax of a few new query rows over the valid part of a
     K/V cache: the CPU path and the test oracle of `sdpa_kvcache`.
 
@@ -485,10 +522,18 @@ def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=F
     page pools [num_pages, Hkv, page_size, D] (any page_size >= 1): the pages
     are gathered into a dense cache of max_pages * page_size rows first
     (`gather_pages`; dead entries may name any page, their rows are masked).
+    float8_e4m3fn caches take optional per-head fp32 scales [Hkv]: key row j
+    of K/V head h is float(k_cache[.., h, j, :]) * k_scale[h] (V alike, None =
+    ones); a scale with any other cache dtype raises ValueError.
     Returns o in q's dtype (and lse [B, H, Nq] fp32)."""
+    fp8 = _check_fp8_scales(k_cache, v_cache, k_scale, v_scale)
     if block_table is not None:
         assert v_cache.shape == k_cache.shape and block_table.shape[0] == q.shape[0]
+        if fp8:  # gather bytes
+            k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
         k_cache, v_cache = gather_pages(k_cache, block_table), gather_pages(v_cache, block_table)
+        if fp8:
+            k_cache, v_cache = k_cache.view(_FP8), v_cache.view(_FP8)
     B, H, Nq, D = q.shape
     Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
     assert v_cache.shape == k_cache.shape and H % Hkv == 0 and Nmax >= Nq
@@ -502,11 +547,13 @@ def kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal=True, return_lse=F
     dead = keys[None, None, :] > last[:, :, None]  # [B, Nq, Nmax]
     slack = keys[None, :] >= ln[:, None]  # [B, Nmax]
 
+    # NaN bytes of the slack become NaN floats here and are masked below
+    kf = dequantize_fp8(k_cache, k_scale) if fp8 else k_cache.float()
     qg = q.float().reshape(B, Hkv, G, Nq, D)
-    s = torch.einsum('bkgqd,bknd->bkgqn', qg, k_cache.float()) / math.sqrt(D)
+    s = torch.einsum('bkgqd,bknd->bkgqn', qg, kf) / math.sqrt(D)
     s = s.masked_fill(dead[:, None, None], -float('inf'))
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.unsqueeze(-1))
-    vf = v_cache.float().masked_fill(slack[:, None, :, None], 0.0)
+    vf = (dequantize_fp8(v_cache, v_scale) if fp8 else v_cache.float()).masked_fill(slack[:, None, :, None], 0.0)
     o = torch.einsum('bkgqn,bknd->bkgqd', p, vf).reshape(B, H, Nq, D).to(q.dtype)
     return (o, lse.reshape(B, H, Nq)) if return_lse else o

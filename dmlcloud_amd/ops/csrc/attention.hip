@@ -2065,5 +2065,6 @@ void attn_decode_tiled(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_l
 #include "attention_d128.h"
 #include "attention_decode_d128.h"
 #include "attention_kvcache_append.h"
+#include "attention_decode_fp8.h"
 
 } // namespace dmlamd

@@ -84,6 +84,13 @@ int64_t attn_decode_tiled_workspace_floats(int64_t B, int64_t Hkv, int64_t R, in
                                            int64_t D);
 int64_t attn_decode_tiled_splits(int64_t B, int64_t Hkv, int64_t R, int64_t Nmax,
                                  int64_t num_splits, int64_t device);
+void attn_decode_fp8(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor kv_len, at::Tensor o,
+                     at::Tensor lse, at::Tensor ws, double scale, bool causal, int64_t num_splits,
+                     c10::optional<at::Tensor> k_scale, c10::optional<at::Tensor> v_scale,
+                     c10::optional<at::Tensor> block_table);
+void kvcache_append_fp8(at::Tensor k_new, at::Tensor v_new, at::Tensor k_cache, at::Tensor v_cache,
+                        at::Tensor kv_len, c10::optional<at::Tensor> k_scale,
+                        c10::optional<at::Tensor> v_scale, c10::optional<at::Tensor> block_table);
 
 } // namespace dmlamd
 
@@ -167,4 +174,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "The split count attn_decode_tiled runs with (num_splits, or the automatic choice for 0)",
         py::arg("B"), py::arg("Hkv"), py::arg("R"), py::arg("Nmax"), py::arg("num_splits"),
         py::arg("device"));
+  m.def("attn_decode_fp8", &dmlamd::attn_decode_fp8,
+        "attn_decode_tiled over a float8_e4m3fn K/V cache (dense or paged, D=64 or 128, any R): the "
+        "bytes are dequantised to bf16 in registers, key row j of K/V head h is "
+        "float(cache[.., h, j, :]) * scale[h] with optional fp32 [Hkv] device tensors k_scale, "
+        "v_scale (none = ones). Sized by attn_decode_tiled_splits / _workspace_floats",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"), py::arg("o"),
+        py::arg("lse"), py::arg("ws"), py::arg("scale"), py::arg("causal"), py::arg("num_splits"),
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("block_table") = py::none());
+  m.def("kvcache_append_fp8", &dmlamd::kvcache_append_fp8,
+        "kvcache_append into a float8_e4m3fn cache: element x is stored as "
+        "e4m3_rne(clamp(float(x) / scale[h], -448, 448)); one launch, no host sync",
+        py::arg("k_new"), py::arg("v_new"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("kv_len"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(),
+        py::arg("block_table") = py::none());
 }

@@ -61,6 +61,20 @@ block_table=None)` writes the new tokens' K/V rows into a dense or paged
 cache in one launch, positions resolved on the device
 (ops/csrc/attention_kvcache_append.h). Verified in
 tests/test_gpu_attention_kvcache_paged.py.
+
+FP8 cache: k_cache and v_cache may be `torch.float8_e4m3fn` (the MI355X's
+native OCP e4m3), dense or paged, with optional per-K/V-head fp32 scales
+`k_scale`, `v_scale` [Hkv] on the device (None = ones): key row j of head h
+is float(k_cache[.., h, j, :]) * k_scale[h], V alike. q and the appended rows
+stay bf16. `sdpa_kvcache(..., k_scale=, v_scale=)` runs one split-KV kernel
+for every R and both D that dequantises the bytes to bf16 in registers (exact)
+and keeps the bf16 MFMAs, folding k_scale into the softmax scale and v_scale
+into the epilogue; `kvcache_append(..., k_scale=, v_scale=)` stores
+e4m3_rne(clamp(float(x) / scale[h], -448, 448)) in one launch
+(ops/csrc/attention_decode_fp8.h). The scales are read on the device, so a
+captured call follows them. A scale passed with a cache of another dtype
+raises ValueError. Verified in tests/test_attention_kvcache_fp8_ref.py and
+tests/test_gpu_attention_kvcache_fp8.py.
 """
 
 import math
@@ -101,6 +115,22 @@ class _SdpaFn(torch.autograd.Function):
 
 
 _INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+_FP8 = torch.float8_e4m3fn
+
+
+def _fp8_caches(k_cache, v_cache, k_scale, v_scale):
+    """True for an e4m3 cache pair; a scale with any other cache is an error."""
+    fp8 = k_cache.dtype == _FP8 and v_cache.dtype == _FP8
+    if not fp8 and (k_scale is not None or v_scale is not None):
+        raise ValueError('k_scale / v_scale go with float8_e4m3fn caches only')
+    return fp8
+
+
+def _fp8_scale_ok(scale, like, n_kv_head):
+    # what the native kernels read: fp32 [Hkv] on the device (the wrapper makes it contiguous)
+    return scale is None or (
+        scale.dtype == torch.float32 and scale.shape == (n_kv_head,) and scale.device == like.device
+    )
 
 
 def _usable(q, k, v, doc_start=None, causal=True):
@@ -258,8 +288,11 @@ def sdpa(q, k, v, causal: bool = True, doc_start=None):
     return F.scaled_dot_product_attention(q, k, v, attn_mask=document_mask(doc_start, causal), **gqa)
 
 
-def _kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None):
+def _kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None, k_scale=None, v_scale=None):
+    fp8 = _fp8_caches(k_cache, v_cache, k_scale, v_scale)
     if not fused_attention_enabled():
+        return False
+    if fp8 and not (k_cache.dim() == 4 and all(_fp8_scale_ok(s, q, k_cache.shape[1]) for s in (k_scale, v_scale))):
         return False
     ok = (
         q.is_cuda
@@ -273,8 +306,7 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None):
         and q.shape[1] % k_cache.shape[1] == 0
         and (q.shape[1] // k_cache.shape[1]) * q.shape[2] >= 1
         and v_cache.shape == k_cache.shape
-        and k_cache.dtype == q.dtype
-        and v_cache.dtype == q.dtype
+        and (fp8 or (k_cache.dtype == q.dtype and v_cache.dtype == q.dtype))
         and k_cache.device == q.device
         and v_cache.device == q.device
         and all(t.stride(-1) == 1 for t in (q, k_cache, v_cache))
@@ -298,7 +330,7 @@ def _kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None):
     )
 
 
-def fused_kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None) -> bool:
+def fused_kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None, k_scale=None, v_scale=None) -> bool:
     """True when `sdpa_kvcache(q, k_cache, v_cache, kv_len, block_table=...)`
     will run the native split-KV kernels, False when it will run the
     pure-torch reference: bf16 device tensors, q [B, H, Nq, D] with D = 64 or
@@ -307,17 +339,30 @@ def fused_kvcache_usable(q, k_cache, v_cache, kv_len, block_table=None) -> bool:
     without a table caches [B, Hkv, Nmax, D] with Hkv dividing H and
     Nmax >= Nq; with one, pools [num_pages, Hkv, page_size, D] with Hkv
     dividing H and page_size a positive multiple of 32, and an integer
-    [B, max_pages] table on q's device with max_pages * page_size >= Nq."""
-    return bool(_kvcache_usable(q, k_cache, v_cache, kv_len, block_table))
+    [B, max_pages] table on q's device with max_pages * page_size >= Nq.
+    The caches are bf16 like q, or both float8_e4m3fn, then with `k_scale` and
+    `v_scale` each None or an fp32 [Hkv] tensor on q's device (a scale with a
+    cache of another dtype raises ValueError, as the call itself does)."""
+    return bool(_kvcache_usable(q, k_cache, v_cache, kv_len, block_table, k_scale, v_scale))
 
 
 def _vector_loadable(t):
-    # the kernels read rows as 16-byte vectors
-    return t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1])
+    # the kernels read rows as 16-byte vectors: 8 bf16 or 16 e4m3 elements
+    n = 16 // t.element_size()
+    return t.data_ptr() % 16 == 0 and all(s % n == 0 for s in t.stride()[:-1])
 
 
 def sdpa_kvcache(
-    q, k_cache, v_cache, kv_len, causal: bool = True, num_splits: int = 0, return_lse: bool = False, block_table=None
+    q,
+    k_cache,
+    v_cache,
+    kv_len,
+    causal: bool = True,
+    num_splits: int = 0,
+    return_lse: bool = False,
+    block_table=None,
+    k_scale=None,
+    v_scale=None,
 ):
     """Attention of new query rows over a partly filled K/V cache: one row
     (decoding), a few (speculative verification) or a whole chunk of a
@@ -359,14 +404,22 @@ def sdpa_kvcache(
     block_table)`). Everything else (other head dims, other dtypes, other page
     sizes) runs `_attention_ref.kvcache_attention_ref`.
 
+    FP8 cache: k_cache and v_cache may both be float8_e4m3fn, with `k_scale`
+    and `v_scale` None (ones) or fp32 [Hkv] tensors on q's device: key row j
+    of K/V head h is float(k_cache[.., h, j, :]) * k_scale[h], V alike. The
+    native path (`_C.attn_decode_fp8`, one kernel for every R, both D, dense
+    and paged) reads the scales on the device, so they may change between
+    replays of a captured call. A scale with a cache of another dtype raises
+    ValueError.
+
     Returns o [B, H, Nq, D] in q's dtype, and with return_lse=True also
     lse [B, H, Nq] fp32."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k_cache, v_cache)):
         raise RuntimeError('sdpa_kvcache is forward only: call it under torch.no_grad() or detach its inputs')
-    if not _kvcache_usable(q, k_cache, v_cache, kv_len, block_table):
+    if not _kvcache_usable(q, k_cache, v_cache, kv_len, block_table, k_scale, v_scale):
         from ._attention_ref import kvcache_attention_ref
 
-        return kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal, return_lse, block_table)
+        return kvcache_attention_ref(q, k_cache, v_cache, kv_len, causal, return_lse, block_table, k_scale, v_scale)
     B, H, Nq, D = q.shape
     Hkv, Nmax = k_cache.shape[1], k_cache.shape[2]
     q, k_cache, v_cache = (t if _vector_loadable(t) else t.contiguous() for t in (q, k_cache, v_cache))
@@ -376,6 +429,17 @@ def sdpa_kvcache(
         if block_table.dtype != torch.int32 or not block_table.is_contiguous():
             block_table = block_table.detach().to(torch.int32).contiguous()
         Nmax = block_table.shape[1] * k_cache.shape[2]  # the capacity
+    if k_cache.dtype == _FP8:
+        splits = _C.attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device())
+        o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
+        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+        # the tiled kernels' partial layout; every element the merge reads is written
+        ws = torch.empty(_C.attn_decode_tiled_workspace_floats(B, Hkv, R, splits, D), dtype=torch.float32, device=q.device)
+        k_scale, v_scale = (None if s is None else s.detach().contiguous() for s in (k_scale, v_scale))
+        _C.attn_decode_fp8(
+            q, k_cache, v_cache, kv_len, o, lse, ws, 1.0 / math.sqrt(D), causal, splits, k_scale, v_scale, block_table
+        )
+        return (o, lse) if return_lse else o
     if block_table is not None or R > 16 or D == 128:
         splits = _C.attn_decode_tiled_splits(B, Hkv, R, Nmax, num_splits, q.get_device())
         o = torch.empty(B, H, Nq, D, dtype=q.dtype, device=q.device)
@@ -393,7 +457,14 @@ def sdpa_kvcache(
     return (o, lse) if return_lse else o
 
 
-def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
+def _fp8_storable(k_cache, v_cache, k_new, k_scale, v_scale):
+    # the append stores 8 bytes per lane; the scales as the kernels read them
+    return all(
+        t.data_ptr() % 8 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]) for t in (k_cache, v_cache)
+    ) and all(_fp8_scale_ok(s, k_new, k_new.shape[1]) for s in (k_scale, v_scale))
+
+
+def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None, k_scale=None, v_scale=None):
     """Write the K and V rows of Nq new tokens per batch row into a K/V cache,
     in place, at the positions `sdpa_kvcache` gives the same query rows.
 
@@ -415,7 +486,14 @@ def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
     multiples of 8 elements; they are written in place and cannot be copied),
     extension built, no DMLCLOUD_DISABLE_FUSED_ATTN. k_new / v_new that are not
     16-byte loadable are copied first. Everything else runs
-    `_attention_ref.kvcache_append_ref`, two index writes."""
+    `_attention_ref.kvcache_append_ref`, two index writes.
+
+    FP8 cache: with float8_e4m3fn caches, element x of head h is stored as
+    e4m3_rne(clamp(float(x) / scale[h], -448, 448)), `k_scale` / `v_scale`
+    None (ones) or fp32 [Hkv] on the device (`_C.kvcache_append_fp8`; the
+    caches then need base and strides that are multiples of 8 bytes). A scale
+    with a cache of another dtype raises ValueError."""
+    fp8 = _fp8_caches(k_cache, v_cache, k_scale, v_scale)
     tensors = (k_new, v_new, k_cache, v_cache)
     native = (
         fused_attention_enabled()
@@ -424,9 +502,13 @@ def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
         and k_new.dim() == 4
         and k_cache.dim() == 4
         and k_new.shape[-1] in (64, 128)
-        and all(t.dtype == torch.bfloat16 and t.device == k_new.device and t.stride(-1) == 1 for t in tensors)
-        and _vector_loadable(k_cache)
-        and _vector_loadable(v_cache)
+        and all(t.dtype == torch.bfloat16 for t in (tensors[:2] if fp8 else tensors))
+        and all(t.device == k_new.device and t.stride(-1) == 1 for t in tensors)
+        and (
+            _fp8_storable(k_cache, v_cache, k_new, k_scale, v_scale)
+            if fp8
+            else _vector_loadable(k_cache) and _vector_loadable(v_cache)
+        )
         and kv_len.dtype in _INT_DTYPES
         and kv_len.device == k_new.device
         and (block_table is None or (block_table.dtype in _INT_DTYPES and block_table.device == k_new.device))
@@ -434,11 +516,15 @@ def kvcache_append(k_new, v_new, k_cache, v_cache, kv_len, block_table=None):
     if not native:
         from ._attention_ref import kvcache_append_ref
 
-        return kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table)
+        return kvcache_append_ref(k_new, v_new, k_cache, v_cache, kv_len, block_table, k_scale, v_scale)
     k_new, v_new = (t if _vector_loadable(t) else t.contiguous() for t in (k_new, v_new))
     kv_len = kv_len.detach().to(torch.int32).contiguous()  # no-ops for an int32 tensor
     if block_table is not None and (block_table.dtype != torch.int32 or not block_table.is_contiguous()):
         block_table = block_table.detach().to(torch.int32).contiguous()
+    if fp8:
+        k_scale, v_scale = (None if s is None else s.detach().contiguous() for s in (k_scale, v_scale))
+        _C.kvcache_append_fp8(k_new.detach(), v_new.detach(), k_cache, v_cache, kv_len, k_scale, v_scale, block_table)
+        return
     _C.kvcache_append(k_new.detach(), v_new.detach(), k_cache, v_cache, kv_len, block_table)
 
 

@@ -27,7 +27,9 @@ ops.fused_attn.sdpa_kvcache (the split-KV decode kernels on the device).
 GPT2.extend instead (the tiled KV-cache kernels once a chunk has more than
 16 query columns per K/V head). --page-size P keeps the cache in pages of P
 rows read through a block table (GPT2.init_paged_cache; the paged kernels
-for P a multiple of 32).
+for P a multiple of 32). --kv-dtype fp8 keeps that cache, dense or paged, as
+e4m3 bytes with unit scales (the fp8 split-KV kernel and the quantising
+append).
 """
 
 import argparse
@@ -161,6 +163,9 @@ def main():
     parser.add_argument(
         '--page-size', type=int, default=None, metavar='P', help='with --sample: a paged K/V cache with pages of P rows'
     )
+    parser.add_argument(
+        '--kv-dtype', choices=('bf16', 'fp8'), default='bf16', help='with --sample: fp8 keeps the K/V cache as e4m3 bytes'
+    )
     args = parser.parse_args()
 
     init_process_group_auto()
@@ -170,7 +175,10 @@ def main():
     if args.sample > 0 and torch.distributed.get_rank() == 0:
         model = pipeline.models['gpt2'].module
         prompt = torch.arange(1, 9, device=next(model.parameters()).device).unsqueeze(0)
-        out = model.generate(prompt, args.sample, prefill_chunk=args.prefill_chunk, page_size=args.page_size)
+        kv_dtype = torch.float8_e4m3fn if args.kv_dtype == 'fp8' else None
+        out = model.generate(
+            prompt, args.sample, prefill_chunk=args.prefill_chunk, page_size=args.page_size, kv_dtype=kv_dtype
+        )
         print('sampled tokens:', out[0, 8:].tolist())
 
 

@@ -13,6 +13,7 @@ torch SDPA with enable_gqa=True, and the plain MHA row at the same H.
     python tools/bench_attn.py --decode-tiled   # sdpa_kvcache, more than 16 columns
     python tools/bench_attn.py --decode-d128    # sdpa_kvcache at head dim 128
     python tools/bench_attn.py --decode-paged   # paged cache against dense; kvcache_append
+    python tools/bench_attn.py --decode-fp8     # fp8 (e4m3) cache against bf16; quantising append
     python tools/bench_attn.py --d128     # head dim 128: native against the torch SDPA fallback
 """
 
@@ -403,6 +404,89 @@ def main_decode_paged():
     bench_append(8, 12, 256, 64)
 
 
+def _fp8_scales(hkv):
+    return 0.0071 + 0.0023 * torch.arange(hkv, dtype=torch.float32, device=DEV)
+
+
+def bench_decode_fp8(b, h, hkv, nq, nmax, d, caches=1, rounds=3):
+    """Nq new causal rows over a FULL dense cache of nmax keys: the bf16 native
+    kernels | the fp8 kernel on the same keys quantised, alternated over
+    `rounds` rounds in one process. caches > 1 rotates the calls of both
+    columns over that many distinct cache pairs, so that no call finds its
+    keys in the 256 MB Infinity Cache."""
+    from dmlcloud_amd.ops._attention_ref import quantize_fp8
+    from dmlcloud_amd.ops.fused_attn import fused_kvcache_usable, sdpa_kvcache
+
+    torch.manual_seed(0)
+    mk = lambda heads, n: (torch.randn(b, heads, n, d, device=DEV) * 0.5).to(torch.bfloat16)
+    q, ks, vs = mk(h, nq), _fp8_scales(hkv), _fp8_scales(hkv) * 2
+    kv_len = torch.full((b,), nmax, dtype=torch.int32, device=DEV)
+    bf16 = [(mk(hkv, nmax), mk(hkv, nmax)) for _ in range(caches)]
+    fp8 = [(quantize_fp8(k, ks), quantize_fp8(v, vs)) for k, v in bf16]
+    assert fused_kvcache_usable(q, *fp8[0], kv_len, None, ks, vs)
+    turn = {'bf16': 0, 'fp8': 0}
+
+    def run(name):
+        i = turn[name] = (turn[name] + 1) % caches
+        if name == 'bf16':
+            return sdpa_kvcache(q, *bf16[i], kv_len)
+        return sdpa_kvcache(q, *fp8[i], kv_len, k_scale=ks, v_scale=vs)
+
+    mb = lambda pairs: sum(t.numel() * t.element_size() for p in pairs for t in p) / 2**20
+    with torch.no_grad():
+        times = {name: [] for name in turn}
+        for _ in range(rounds):
+            for name in turn:
+                times[name].append(time_fn(lambda: run(name), reps=200, warmup=20))
+    print(
+        f'DECODE-FP8 D={d} B={b} H={h} Hkv={hkv} Nq={nq} Nmax={nmax} caches={caches} '
+        f'({mb(bf16):.0f} MB bf16, {mb(fp8):.0f} MB fp8): ' + ' | '.join(f'{name} {_spread(ts)}' for name, ts in times.items()),
+        flush=True,
+    )
+
+
+def bench_append_fp8(b, hkv, nq, d, nmax=1024, rounds=3):
+    """kvcache_append into a bf16 dense cache against the quantising append
+    into an fp8 one (dense, and paged at page_size 64), alternated."""
+    from dmlcloud_amd.ops.fused_attn import kvcache_append
+
+    torch.manual_seed(0)
+    qkv = torch.randn(b, nq, 3 * hkv * d, device=DEV).to(torch.bfloat16)
+    k_new, v_new = (t.view(b, nq, hkv, d).transpose(1, 2) for t in qkv.split(hkv * d, dim=2)[1:])
+    k, v = (torch.zeros(b, hkv, nmax, d, dtype=torch.bfloat16, device=DEV) for _ in range(2))
+    k8, v8 = (torch.zeros(b, hkv, nmax, d, dtype=torch.uint8, device=DEV).view(torch.float8_e4m3fn) for _ in range(2))
+    kp, vp = (torch.zeros_like(t).view(b * nmax // 64, hkv, 64, d) for t in (k8, v8))
+    table = torch.randperm(b * nmax // 64, device=DEV).to(torch.int32).view(b, nmax // 64)
+    kv_len = torch.full((b,), 512 + nq, dtype=torch.int32, device=DEV)
+    s = dict(k_scale=_fp8_scales(hkv), v_scale=_fp8_scales(hkv) * 2)
+    fns = {
+        'bf16 dense': lambda: kvcache_append(k_new, v_new, k, v, kv_len),
+        'fp8 dense': lambda: kvcache_append(k_new, v_new, k8, v8, kv_len, **s),
+        'fp8 paged 64': lambda: kvcache_append(k_new, v_new, kp, vp, kv_len, table, **s),
+    }
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            times[name].append(time_fn(fn, reps=200, warmup=20))
+    print(
+        f'APPEND-FP8 B={b} Hkv={hkv} Nq={nq} D={d}: ' + ' | '.join(f'{name} {_spread(ts)}' for name, ts in times.items()),
+        flush=True,
+    )
+
+
+def main_decode_fp8():
+    bench_decode_fp8(8, 12, 12, 1, 1024, 64)
+    bench_decode_fp8(8, 32, 8, 1, 4096, 64)
+    bench_decode_fp8(1, 12, 12, 512, 4096, 64)
+    bench_decode_fp8(8, 6, 6, 1, 4096, 128)
+    bench_decode_fp8(1, 8, 8, 512, 4096, 128)
+    # 10 x 64 MB of bf16 K and V per column (10 x 32 MB fp8): past the Infinity Cache
+    bench_decode_fp8(8, 32, 8, 1, 4096, 64, caches=10)
+    bench_decode_fp8(8, 16, 8, 1, 4096, 128, caches=5)
+    bench_append_fp8(64, 12, 1, 64)
+    bench_append_fp8(8, 12, 256, 64)
+
+
 def main_gqa():
     bench_gqa(64, 12, 4, 1024)  # the GPT-2 shape with 4 K/V heads
     bench_gqa(64, 12, 1, 1024)  # ... and as MQA
@@ -473,6 +557,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if '--decode-paged' in sys.argv[1:]:
         main_decode_paged()
+        sys.exit(0)
+    if '--decode-fp8' in sys.argv[1:]:
+        main_decode_fp8()
         sys.exit(0)
     if '--decode' in sys.argv[1:]:
         main_decode()
